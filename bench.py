@@ -2,6 +2,13 @@
 """bench.py -- DuPL training-step throughput on MI355X (BASELINE.json metric: training img/s at 448^2).
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched through torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (also write what the last timed step computed, DIR/<name>.npy)
+    python bench.py ... --full                             (also every side measurement and check, see below)
+
+A plain run sets up the main workload, runs W warm-up and K timed steps and prints the line.  --full adds what takes runs of
+its own: the roofline / per-family kernel figures, the exact-f32 measurement, the second (N = 1) or listed (N > 1)
+configuration, the exchange checks of N > 1 (exposed communication, devices seen, bit-identical parameters) and the CPU
+baseline; --no-roofline / --no-exact-f32 / --no-second / --no-listed / --cpu-baseline skip leave single legs out of it.
 
 A "step" is one full iteration of the reference loop (train_final_voc.py:174-472 / train_final_coco.py:170-462) on a
 synthetic batch that is already resident in HBM: ms-CAM for both students (3 scales x flip), dual-student
@@ -17,8 +24,8 @@ weak-scaling curve):
     N = 2   configs[2]  VOC2012  448^2, deit_base_patch16_224, 2 img/GPU (global 4)
     N = 4   configs[3]  MSCOCO14 448^2, 81 classes,            2 img/GPU (global 8)
     N = 8   configs[4]  MSCOCO14 448^2, vit_base_patch16_224,  2 img/GPU (global 16)
-(other N: the COCO 2 img/GPU workload).  --dataset / --batch / --backbone override the main workload.  Rank 0 prints
-ONE JSON line.
+(other N: the COCO 2 img/GPU workload; --full only).  --dataset / --batch / --backbone override the main workload.  Rank 0
+prints ONE JSON line.
 """
 from __future__ import annotations
 
@@ -55,6 +62,36 @@ CONFIG_BY_N = {1: ("voc", 4, "deit_base_patch16_224", "configs[1]"),
                4: ("coco", 2, "deit_base_patch16_224", "configs[3]"),
                8: ("coco", 2, "vit_base_patch16_224", "configs[4]")}
 DEFAULT_N_ITER = {"voc": 5000, "coco": 20000}    # phase B of either schedule (PTC + PAR refinement + cross seg loss)
+DUMP_BUDGET = 60 << 20                           # --dump-outputs: bytes of all files together (< 64 MB)
+
+
+def dump_outputs(path, out, params):
+    """--dump-outputs: what a caller of train_step receives from the last timed step -- every tensor of its result dict
+    (losses, logits, feature maps, CAMs, label maps; lists as <name>_<i>) and the updated parameters of both students
+    (`params`, the flat buffer) -- as <path>/<name>.npy, float32 (float64 stays float64).  An array larger than its share of
+    DUMP_BUDGET is replaced by the elements at fixed seeded positions (the same positions in every run), so that two builds
+    can be compared output for output.  Shares: smallest array first, each may take an equal part of the budget that the
+    arrays before it left, so everything small is written whole.  Returns {name: elements written}."""
+    import numpy as np
+    arrays = {}
+    for k, v in out.items():
+        for i, t in enumerate(v if isinstance(v, (list, tuple)) else [v]):
+            if torch.is_tensor(t):
+                arrays[f"{k}_{i}" if isinstance(v, (list, tuple)) else k] = t
+    arrays["params"] = params
+    os.makedirs(path, exist_ok=True)
+    left, written = DUMP_BUDGET, {}
+    for i, (name, t) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].numel())):
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        cap = (left // (len(arrays) - i) - 1024) // t.element_size()       # 1024: room for the .npy header
+        if t.numel() > cap:
+            idx = torch.randint(0, t.numel(), (cap,), generator=torch.Generator().manual_seed(0))
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+        left -= t.numel() * t.element_size() + 1024
+        written[name] = t.numel()
+    return written
 
 
 def parse():
@@ -91,7 +128,17 @@ def parse():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for --gpus > 1 (nccl = RCCL over xGMI; gloo only exists so that the "
                          "multi-rank control flow can be exercised by two ranks sharing one GPU in the tests)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the main measurement also run the side legs: roofline, exact-f32, second / listed "
+                         "configuration, the N > 1 exchange checks and the CPU baseline (each can be left out by its --no-* flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32; arrays too large for the "
+                         f"{DUMP_BUDGET >> 20} MiB budget as a fixed seeded sample of their elements); that step starts from the "
+                         "seeded initial model and optimiser state, so its inputs are the same in every run")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def self_launch(args):
@@ -486,7 +533,7 @@ class Workload:
         from dupl_amd.ddp import DistributedDataParallel
         from dupl_amd.synthetic import synthetic_batch
         from dupl_amd import trainer
-        self.args, self.world, self.local = args, world, local
+        self.args, self.world, self.rank, self.local = args, world, rank, local
         self.dataset, self.batch, self.backbone, self.n_iter = dataset, batch, backbone, n_iter
         self.dev = dev = torch.device("cuda", local)
         self.C = C = 20 if dataset == "voc" else 80
@@ -544,9 +591,18 @@ class Workload:
             dist.barrier(device_ids=[self.local]) if self.args.backend == "nccl" else dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(self, label):
-        """W warm-up steps, then EXACTLY K steps between barrier + synchronize, max over ranks."""
+    def measure(self, label, dump_dir=None):
+        """W warm-up steps, then EXACTLY K steps between barrier + synchronize, max over ranks; with dump_dir, rank 0 then
+        writes what the last of them computed (dump_outputs) before anything else runs on the model.
+        The dumped step starts from the seeded initial state (model + optimiser state_dict, cloned before the warm-up and put
+        back with the clock stopped), so that all its inputs are the same in every run: default-mode gradients accumulate in
+        fp32 atomics, and over many steps training amplifies their order-dependent last bits into different parameters (two
+        runs, 100 steps: label maps apart at hundreds of pixels).  The step itself runs in the caller's mode."""
         args, world = self.args, self.world
+        start = None
+        if dump_dir is not None:
+            torch.cuda.synchronize()
+            start = ({k: v.detach().clone() for k, v in self.model.state_dict().items()}, self.optim.state_dict())
         log(f"[{label}] {self.dataset} {self.batch} img/GPU {self.backbone} on {self.dev}; {args.warmup} warm-up step(s)")
         for i in range(args.warmup):
             tw = time.perf_counter()
@@ -559,9 +615,19 @@ class Workload:
         self.barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
+            if start is not None and i == args.steps - 1:
+                self.barrier()
+                tp = time.perf_counter()
+                self.model.load_state_dict(start[0])
+                self.optim.load_state_dict(start[1])
+                self.barrier()
+                t0 += time.perf_counter() - tp          # the restore is not part of a step
             out = self.step(args.warmup + i)
         self.barrier()
         dt = time.perf_counter() - t0
+        if dump_dir is not None and self.rank == 0:
+            n = dump_outputs(dump_dir, out, self.model.flat_storage.data)
+            log(f"[{label}] outputs of the last timed step: {len(n)} arrays, {sum(n.values())} elements -> {dump_dir}")
         comm = {"world": world, "backend": (args.backend + ("(RCCL)" if args.backend == "nccl" else "")) if world > 1 else "none",
                 "grad_bytes_per_rank": self.grad_bytes, "allreduce_bytes": 0, "allreduce_calls": 0, "comm_exposed_ms": 0.0}
         if world > 1:
@@ -572,6 +638,8 @@ class Workload:
             st = red.pop_stats()
             comm["allreduce_bytes"] = st["allreduce_bytes"] // max(1, args.steps)      # per step, this rank
             comm["allreduce_calls"] = st["allreduce_calls"] // max(1, args.steps)
+            comm["comm_exposed_ms"] = None          # measured by --full (one extra step of its own)
+        if world > 1 and args.full:
             # exposed communication: one extra step with the step's compute drained before the waits of finish()
             # (profiling inserts a stream join, so it runs outside the timed region)
             red.profile = True
@@ -618,7 +686,7 @@ class Workload:
 def main():
     args = parse()
     world, rank, local = build_world(args)
-    # main workload: configs[1] per rank at every N (weak scaling); the configuration listed for N > 1 is measured second
+    # main workload: configs[1] per rank at every N (weak scaling); the configuration listed for N > 1 is measured second (--full)
     d_ds, d_b, d_bb, d_cfg = CONFIG_BY_N[1]
     dataset = args.dataset or d_ds
     batch = args.batch or d_b
@@ -628,10 +696,10 @@ def main():
         d_cfg = "configs[1] on every rank (weak scaling of the N = 1 workload)"
     n_iter = args.n_iter if args.n_iter is not None else DEFAULT_N_ITER[dataset]
 
-    from dupl_amd import engine
+    from dupl_amd import engine, ops
     gemm_mode = engine.GEMM_MODE
     wl = Workload(args, world, rank, local, dataset, batch, backbone, n_iter)
-    res = wl.measure("main")
+    res = wl.measure("main", dump_dir=args.dump_outputs)
     ms, imgs_per_s, phase, C = res["ms"], res["value"], wl.phase, wl.C
     guard_main = wl.model.flat_storage.guard          # of the main workload (later legs build other models)
 
@@ -639,7 +707,7 @@ def main():
     flop_exec = FLOP_PER_IMG_PHASE_AB - (0.0 if args.no_share_encoder else FLOP_SHARED_PASS) + \
         (FLOP_PHASE_C_AUG if phase == "C" else 0.0)
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         wl.model.enable_dual_stream(False)   # per-kernel durations are only meaningful without a co-running stream
         timer = GemmTimer()
         timer.install()
@@ -718,7 +786,7 @@ def main():
     # the same workload on the exact-f32 MFMA kernels (DUPL_GEMM=f32): the number to read if the f16x3 split products are
     # not accepted as the reference's fp32 arithmetic
     exact = None
-    if gemm_mode == "f16x3" and not args.no_exact_f32:
+    if args.full and gemm_mode == "f16x3" and not args.no_exact_f32:
         engine.set_gemm_mode("f32")
         rx = wl.measure("exact-f32")
         engine.set_gemm_mode("f16x3")
@@ -728,7 +796,7 @@ def main():
 
     listed_cfg = None
     l_ds, l_b, l_bb, l_name = CONFIG_BY_N.get(world, ("coco", 2, "deit_base_patch16_224", "COCO 2 img/GPU (no BASELINE entry for this N)"))
-    if world > 1 and not args.no_listed and (dataset, batch, backbone) != (l_ds, l_b, l_bb):
+    if args.full and world > 1 and not args.no_listed and (dataset, batch, backbone) != (l_ds, l_b, l_bb):
         del wl
         torch.cuda.empty_cache()
         wL = Workload(args, world, rank, local, l_ds, l_b, l_bb, DEFAULT_N_ITER[l_ds])
@@ -741,7 +809,7 @@ def main():
 
     # the metric's second configuration ("COCO bs=8"): timed in the same run on one GPU, with its own ms_per_step
     second = None
-    if world == 1 and not args.no_second and listed and (dataset, batch) == ("voc", 4):
+    if args.full and world == 1 and not args.no_second and listed and (dataset, batch) == ("voc", 4):
         del wl
         torch.cuda.empty_cache()
         w2 = Workload(args, world, rank, local, "coco", 8, backbone, DEFAULT_N_ITER["coco"])
@@ -754,7 +822,7 @@ def main():
         wl = w2
 
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline == "auto":
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline == "auto":
         log("timing the CPU oracle on the host cores (bounded sample: warm-up + thread sweep + timed steps)")
         cpu = cpu_baseline(args, dataset, C)
         log(f"cpu baseline: {cpu}")
@@ -770,7 +838,7 @@ def main():
                           "global_batch": world * batch, "img_per_gpu": batch, "num_classes": C + 1,
                           "n_iter": n_iter, "parallelism": f"dp{world}", "student_streams": 1 if args.single_stream else 2,
                           "shared_scale1_encoder_pass": not args.no_share_encoder, "forward_gemm": gemm_mode,
-                          "deterministic": os.environ.get("DUPL_DETERMINISTIC", "0") == "1",
+                          "deterministic": ops.deterministic(),
                           "loss": round(res["loss"], 5)},
                # schema 2 (round 4): `value` = configs[1] (VOC, 4 img/GPU) on EVERY rank at every N -- a weak-scaling point, NOT the
                # configuration BASELINE.json lists for N > 1 (that one is `listed_config`); `second_config` = COCO 8 img/GPU at

@@ -351,6 +351,37 @@ def test_bench_gpus_n_never_silently_runs_one_rank():
     assert r.returncode != 0 and "WORLD_SIZE=2" in r.stderr and not any(ln.startswith("{") for ln in r.stdout.splitlines())
 
 
+def test_bench_dump_outputs_is_seeded_and_within_budget(tmp_path):
+    """bench.py --dump-outputs: every tensor of the step's result dict (a list as <name>_<i>) plus the parameters, as .npy in
+    float32 (float64 stays float64); small arrays whole and in their shape, the largest ones a seeded sample of their elements --
+    the same elements in every run -- so that the files stay under 64 MB."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    big = torch.arange(16_000_000, dtype=torch.float32)           # integral values: every sampled element shows its position
+    out = {"loss": torch.tensor([3.5]), "cams_1": big.view(4, 20, 400, 500), "fmap_1": -big[:9_000_000].view(4, 750, 3000),
+           "refined_1": torch.arange(4 * 448 * 448).view(4, 448, 448) % 21, "n_uncertain": (torch.tensor(3), torch.tensor(5)),
+           "reg_loss": torch.tensor(0.25, dtype=torch.float64), "note": "not a tensor"}
+    params = torch.linspace(-1.0, 1.0, 20_000_000)
+    n = bench.dump_outputs(str(tmp_path / "a"), out, params)
+    bench.dump_outputs(str(tmp_path / "b"), out, params)
+    names = ["loss", "cams_1", "fmap_1", "refined_1", "n_uncertain_0", "n_uncertain_1", "reg_loss", "params"]
+    assert sorted(os.listdir(tmp_path / "a")) == sorted(k + ".npy" for k in names) and set(n) == set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64e6
+    a = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    for k in names:
+        assert a[k].dtype == (np.float64 if k == "reg_loss" else np.float32) and a[k].size == n[k], k
+        assert np.array_equal(a[k], np.load(tmp_path / "b" / (k + ".npy"))), k
+    assert a["loss"].tolist() == [3.5] and a["n_uncertain_1"].tolist() == 5.0 and a["reg_loss"].tolist() == 0.25
+    assert np.array_equal(a["refined_1"], out["refined_1"].numpy().astype(np.float32))       # 3.2 MB: whole, in its shape
+    for k, src in (("cams_1", big.numpy()), ("fmap_1", -big[:9_000_000].numpy()), ("params", params.numpy())):
+        assert a[k].ndim == 1 and 1_000_000 < a[k].size < src.size and np.isin(a[k], src).all(), k     # its own elements
+    pos = a["cams_1"] / big.numel()            # positions of the sampled elements: spread over the whole array
+    assert pos.min() < 0.01 and pos.max() > 0.99 and abs(pos.mean() - 0.5) < 0.01
+
+
 def test_library_carries_the_digest_of_its_sources_and_a_stale_one_is_refused(monkeypatch):
     """the prebuilt, git-ignored libdupl_hip.so travels to the GPU box with the tree.  Its build identity is
     baked in (dupl_build_digest, written by dupl_amd/build.py) and the ctypes stub compares it with the sources next to it: a

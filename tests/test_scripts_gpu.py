@@ -252,12 +252,12 @@ dist.destroy_process_group()
 
 
 def test_bench_contract_line(dev):
-    """bench.py prints ONE JSON line with the driver's contract keys plus the roofline / cpu_baseline objects (the CPU leg
-    is skipped here to keep the test short; `python bench.py` with no flags runs it)."""
+    """bench.py --full prints ONE JSON line with the driver's contract keys plus the roofline / cpu_baseline objects (the CPU
+    leg is skipped here to keep the test short; `python bench.py --full` with no other flags runs it)."""
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--cpu-baseline", "skip"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--cpu-baseline", "skip"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -306,6 +306,48 @@ def test_bench_contract_line(dev):
     assert cm["world"] == 1 and cm["backend"] == "none" and cm["allreduce_bytes"] == 0 and cm["comm_exposed_ms"] == 0.0
     assert cm["grad_bytes_per_rank"] > 7.0e8 and d["listed_config"] is None
     assert d["config"]["baseline_config"] == "configs[1]" and d["config"]["img_per_gpu"] == 4
+
+
+def test_bench_plain_run_times_only_the_main_workload_and_dumps_its_outputs(dev, tmp_path):
+    """A plain run (no --full) runs W warm-up + exactly K timed steps of the main workload and no side leg; --dump-outputs writes
+    what the last timed step computed, within 64 MB.  That step starts from the seeded initial state, so two runs with the same
+    arguments differ by one step's round-off at most in the default mode (fp32 atomics in the gradients) and not at all
+    under DUPL_DETERMINISTIC=1."""
+    import json
+    import numpy as np
+
+    def run(name, deterministic):
+        env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+        env.pop("DUPL_DETERMINISTIC", None)
+        if deterministic:
+            env["DUPL_DETERMINISTIC"] = "1"
+        out = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(out)], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["warmup"] == 1 and "timed region: 3 steps" in r.stderr and "warm-up step 1" not in r.stderr
+        assert d["config"]["deterministic"] is deterministic
+        assert d["unit"] == "img/s" and d["higher_is_better"] is True and d["dtype"].startswith("f32") and "phase B" in d["metric"]
+        assert abs(d["value"] - 4 * 1000.0 / d["ms_per_step"]) < 0.05 * d["value"]
+        assert all(d[k] is None for k in ("roofline", "exact_f32_path", "second_config", "listed_config", "cpu_baseline"))
+        files = sorted(os.listdir(out))
+        assert sum(os.path.getsize(out / f) for f in files) <= 64e6
+        a = {f[:-4]: np.load(out / f) for f in files}
+        for k in ("loss", "cls_1", "cls_aux_2", "segs_1", "fmap_2", "cams_1", "cams_aux_2", "pseudo_label_aux_1", "refined_2", "params"):
+            assert k in a and a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert a["cls_1"].shape == (4, 20) and a["segs_1"].shape == (4, 21, 28, 28) and a["refined_2"].shape == (4, 448, 448)
+        assert abs(float(a["loss"].sum()) - d["config"]["loss"]) <= 1e-4 * max(1.0, abs(d["config"]["loss"]))
+        return a
+
+    a, b = run("a", False), run("b", False)
+    assert a.keys() == b.keys()
+    for k in a:
+        assert a[k].shape == b[k].shape and np.allclose(b[k], a[k], rtol=1e-5, atol=1e-6 * float(np.abs(a[k]).max())), k
+    c, e = run("c", True), run("d", True)
+    assert c.keys() == a.keys() and all(np.array_equal(c[k], e[k]) for k in c)
 
 
 def test_bench_stale_pmc_profile_is_refused(tmp_path):
@@ -547,7 +589,7 @@ def test_bench_multi_rank_control_flow(dev):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--backend", "gloo", "--cpu-baseline", "skip", "--no-roofline"]
+           "--backend", "gloo", "--full", "--cpu-baseline", "skip", "--no-roofline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -36,6 +36,16 @@ def test_library_exports_every_declared_symbol():
     assert _lib.GemmDesc().struct_size == sizes[0] and _lib.Gemm16Desc().struct_size == sizes[1]
 
 
+def test_segment_count_mirror_matches_the_header():
+    """_lib.ATTN_SEGS_MAX (what ops.attention_fwd16_segs and the engine's merged pass check against) is DUPL_ATTN_SEGS_MAX of
+    include/dupl_hip.h, the size of the arrays the launcher copies the segments into."""
+    import re
+    from dupl_amd import _lib
+    m = re.findall(r"^\s*#\s*define\s+DUPL_ATTN_SEGS_MAX\s+(\d+)\s*$", open(_lib.HEADER).read(), flags=re.M)
+    assert len(m) == 1, m
+    assert _lib.ATTN_SEGS_MAX == int(m[0])
+
+
 def test_product_path_fails_loudly_without_gpu():
     from dupl_amd.model.model_dupl import network
     net = network("tiny_test", num_classes=21, pretrained=False, aux_layer=-3)

@@ -75,6 +75,22 @@ class SplitDesc(ctypes.Structure):
         self.struct_size = ctypes.sizeof(SplitDesc)
 
 
+class CrfDesc(ctypes.Structure):
+    """Mirror of `dupl_crf_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+        ("T", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+        ("img", ctypes.c_void_p), ("Q", ctypes.c_void_p), ("norm", ctypes.c_void_p), ("unary", ctypes.c_void_p),
+        ("out", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+        ("sxy", ctypes.c_float), ("srgb", ctypes.c_float), ("w_g", ctypes.c_float), ("sxy_g", ctypes.c_float),
+        ("w_b", ctypes.c_float), ("sxy_b", ctypes.c_float), ("srgb_b", ctypes.c_float), ("reserved1", ctypes.c_int32),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(CrfDesc)
+
+
 GEMM_A_MCONTIG, GEMM_B_NCONTIG, GEMM_GELU, GEMM_ACCUM = 1, 2, 4, 8
 GEMM_MUL_DGELU, GEMM_RELU, GEMM_MUL_RELUMASK, GEMM_ABS, GEMM_STORE_PRE = 16, 32, 64, 128, 256
 
@@ -108,6 +124,8 @@ def _ctype(decl: str):
         return ctypes.POINTER(SplitDesc)
     if "dupl_gemm_desc" in d:
         return ctypes.POINTER(GemmDesc)
+    if "dupl_crf_desc" in d:
+        return ctypes.POINTER(CrfDesc)
     if "*" in d or d.startswith("dupl_stream_t"):
         return ctypes.c_void_p
     base = d.replace("const", "").split()

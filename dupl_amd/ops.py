@@ -888,3 +888,75 @@ def multilabel_f1_accum(logits: Tensor, label: Tensor, total: Tensor) -> Tensor:
     logits, label = _chk(logits.contiguous()), _chk(label.contiguous().float())
     L().dupl_multilabel_f1_accum(logits.data_ptr(), label.data_ptr(), B, C, total.data_ptr(), _stream())
     return total
+
+
+# ------------------------------------------------------------------------------------------ DenseCRF (csrc/crf.hip)
+def _crf_img(img: Optional[Tensor], H: int, W: int) -> Optional[Tensor]:
+    if img is None:
+        return None
+    assert img.is_cuda and img.dtype == torch.uint8 and tuple(img.shape) == (H, W, 3), "img: (H,W,3) uint8 on the device"
+    return img.contiguous()
+
+
+def crf_norm(img: Optional[Tensor], H: int, W: int, sxy: float, srgb: float = 1.0, device=None) -> Tensor:
+    """n (H,W) with n_i = 1 / sqrt(sum_j k(i,j) + 1e-20) of the Gaussian (img None) or bilateral kernel: the row sums of the
+    dense message, M applied to ones."""
+    device = img.device if img is not None else device
+    img = _crf_img(img, H, W)
+    out = torch.empty((H, W), device=device, dtype=torch.float32)
+    d = _lib.CrfDesc(C=1, H=int(H), W=int(W), img=_p(img), Q=None, norm=None, out=out.data_ptr(), sxy=float(sxy), srgb=float(srgb))
+    L().dupl_crf_message(ctypes.byref(d), _stream())
+    return out
+
+
+def crf_message(img: Optional[Tensor], Q: Tensor, sxy: float, srgb: float = 1.0, normalize=True) -> Tensor:
+    """One application of one DenseCRF kernel, exact over all pixel pairs: out[c,i] = n_i sum_j k(i,j) n_j Q[c,j] with
+    k = exp(-|f_i - f_j|^2 / 2); img None -> Gaussian f = (x,y)/sxy, img (H,W,3) uint8 -> bilateral f = (x/sxy, y/sxy, rgb/srgb).
+    normalize: True = pydensecrf's NORMALIZE_SYMMETRIC (n computed here), False = n = 1, or a precomputed n (H,W) (crf_norm)."""
+    C, H, W = Q.shape
+    Q = _chk(Q.contiguous())
+    img = _crf_img(img, H, W)
+    if normalize is True:
+        n = crf_norm(img, H, W, sxy, srgb, device=Q.device)
+    elif normalize is False or normalize is None:
+        n = None
+    else:
+        n = _chk(normalize)
+        assert n.numel() == H * W
+    out = torch.empty_like(Q)
+    d = _lib.CrfDesc(C=C, H=H, W=W, img=_p(img), Q=Q.data_ptr(), norm=_p(n), out=out.data_ptr(), sxy=float(sxy), srgb=float(srgb))
+    L().dupl_crf_message(ctypes.byref(d), _stream())
+    return out
+
+
+def dense_crf(unary: Tensor, img_u8: Tensor, T: int, w_g: float, sxy_g: float, w_b: float, sxy_b: float, srgb_b: float) -> Tensor:
+    """DenseCRF2D(W,H,C) + setUnaryEnergy(unary) + addPairwiseGaussian(sxy_g, w_g) + addPairwiseBilateral(sxy_b, srgb_b, img, w_b)
+    + inference(T) as the exact mean-field update: unary (C,H,W) fp32, img_u8 (H,W,3) uint8 -> Q (C,H,W)."""
+    C, H, W = unary.shape
+    unary = _chk(unary.contiguous())
+    img = _crf_img(img_u8, H, W)
+    out = torch.empty_like(unary)
+    ws = torch.empty(((2 + 2 * C) * H * W,), device=unary.device, dtype=torch.float32)
+    d = _lib.CrfDesc(C=C, H=H, W=W, T=int(T), img=img.data_ptr(), unary=unary.data_ptr(), out=out.data_ptr(),
+                     workspace=ws.data_ptr(), workspace_bytes=ws.numel() * 4, w_g=float(w_g), sxy_g=float(sxy_g), w_b=float(w_b),
+                     sxy_b=float(sxy_b), srgb_b=float(srgb_b))
+    L().dupl_dense_crf(ctypes.byref(d), _stream())
+    return out
+
+
+def crf_unary(x: Tensor, from_logits: bool = False) -> Tensor:
+    """pydensecrf.utils.unary_from_softmax: U = -log(clip(p, 1e-5, 1)) of x (C,H,W); from_logits: p = softmax_c(x) first."""
+    x = _chk(x.contiguous())
+    C = x.shape[0]
+    U = torch.empty_like(x)
+    L().dupl_crf_unary(x.data_ptr(), U.data_ptr(), C, x.numel() // C, int(bool(from_logits)), _stream())
+    return U
+
+
+def crf_unary_labels(labels: Tensor, n_labels: int, gt_prob: float) -> Tensor:
+    """pydensecrf.utils.unary_from_labels(labels, n_labels, gt_prob, zero_unsure=False): labels (H,W) int64 -> U (n,H,W)."""
+    assert labels.is_cuda and labels.dtype == torch.int64
+    labels = labels.contiguous()
+    U = torch.empty((int(n_labels),) + tuple(labels.shape), device=labels.device, dtype=torch.float32)
+    L().dupl_crf_unary_labels(labels.data_ptr(), U.data_ptr(), int(n_labels), labels.numel(), float(gt_prob), _stream())
+    return U

@@ -1,5 +1,5 @@
-"""Offline multi-scale + flip segmentation inference (reference: tools/eval_seg_voc.py:38-91,154-193 and
-tools/eval_seg_coco_ddp.py:54-139), pre-CRF.
+"""Offline multi-scale + flip segmentation inference and DenseCRF post-processing (reference: tools/eval_seg_voc.py:38-193 and
+tools/eval_seg_coco_ddp.py:54-256).
 
     python -m dupl_amd.tools.eval_seg --model_path work_dir/checkpoints/checkpoint.pth ...   (needs a data loader)
 
@@ -8,7 +8,9 @@ logits are up-sampled to the label size, the flipped half is flipped back and ad
 an element-wise max -- fused into one accumulate kernel per scale (csrc/eval.hip::msc_seg_accum_kernel), so the
 (3, 2, C, H, W) stack the reference builds is never materialised.  `load_checkpoint` reads the reference's checkpoint
 format (torch.save(model.state_dict()) of the DDP-wrapped model: keys prefixed `module.`, train_final_voc.py:514-519).
-DenseCRF post-processing (utils/dcrf.py) is a CPU third-party step and stays outside this package."""
+With `--crf 1` the reference's `crf_proc` follows on the device (`crf_proc` below): DenseCRF(10, 1, 1, 4, 121, 5) on the better
+student's saved logits, `seg_crf` scores and the prediction PNGs.  It is the exact mean-field update (utils/dcrf.py of this
+package, csrc/crf.hip), not pydensecrf's lattice approximation, and its scores have not been compared with pydensecrf's."""
 from collections import OrderedDict
 
 import torch
@@ -125,9 +127,44 @@ def validate(model, data_loader, args, num_classes=21, cat_list=None, keep_logit
     return sc[0], sc[1]
 
 
+def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb_dir, num_classes, dev, process_group=None):
+    """tools/eval_seg_voc.py:94-153 / tools/eval_seg_coco_ddp.py:142-202 on the device, over this rank's `names`: per image the
+    saved logits of `branch` are resized to the JPEG's size, softmax + DenseCRF(10, 1, 1, 4, 121, 5) + argmax run on the device,
+    the label PNG (and the palette PNG) are written and a device ConfusionMatrix is accumulated; with several ranks the
+    matrices are summed.  image_path(name) -> JPEG path; label_of(name, image) -> (H,W) ground truth.  Returns the scores."""
+    import os
+    import numpy as np
+    import torch.distributed as dist
+    from PIL import Image
+    from ..utils import imutils
+    from ..utils.dcrf import DenseCRF
+    post = DenseCRF(iter_max=10, pos_xy_std=1, pos_w=1, bi_xy_std=121, bi_rgb_std=5, bi_w=4)
+    cm = evaluate.ConfusionMatrix(num_classes, dev)
+    for d in (segs_dir, segs_rgb_dir):
+        if d:
+            os.makedirs(d, exist_ok=True)
+    for name in names:
+        logit = np.load(os.path.join(logits_dir, branch, name + ".npy"), allow_pickle=True).item()["msc_seg"]
+        with Image.open(image_path(name)) as im:
+            image = np.ascontiguousarray(np.array(im.convert("RGB")), dtype=np.uint8)
+        H, W, _ = image.shape
+        logit = ops.resize_bilinear(torch.from_numpy(np.ascontiguousarray(logit, dtype=np.float32)).to(dev), H, W)
+        Q = post.from_logits(torch.from_numpy(image).to(dev), logit[0])
+        pred = ops.argmax_channels(Q[None])[0]
+        label = torch.from_numpy(np.ascontiguousarray(label_of(name, image)).astype(np.int64)).to(dev)
+        cm.update(label, pred)
+        pred = pred.cpu().numpy().astype(np.uint8)
+        Image.fromarray(pred).save(os.path.join(segs_dir, name + ".png"))
+        if segs_rgb_dir:
+            Image.fromarray(imutils.encode_cmap(pred).astype(np.uint8)).save(os.path.join(segs_rgb_dir, name + ".png"))
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
+        dist.all_reduce(cm.hist, op=dist.ReduceOp.SUM, group=process_group)
+    return cm.scores()
+
+
 def build_parser(dataset: str = "voc"):
     """The flags of tools/eval_seg_voc.py:26-36 (dataset "voc") or tools/eval_seg_coco_ddp.py:31-46 ("coco"): same names and
-    defaults (tests/golden/cli_flags.json), plus --dataset and --save_logits."""
+    defaults (tests/golden/cli_flags.json), plus --dataset, --save_logits and --crf."""
     import argparse
     voc_ = dataset == "voc"
     p = argparse.ArgumentParser()
@@ -149,15 +186,19 @@ def build_parser(dataset: str = "voc"):
     p.add_argument("--scales", default=[1.0, 1.5, 1.25] if voc_ else [1.0, 1.25, 1.5], help="multi-scale list")
     p.add_argument("--save_logits", default=1, type=int,
                    help="write <run>/segs/logits/<infer_set>/branch{1,2}/<name>.npy = {'msc_seg': ...} like the reference does for "
-                        "its DenseCRF stage (utils/dcrf.py, CPU, outside this package)")
+                        "its DenseCRF stage; --crf 1 reads them back")
+    p.add_argument("--crf", default=0, type=int,
+                   help="1: run the reference's crf_proc on the device after the inference (DenseCRF(10, 1, 1, 4, 121, 5) on the "
+                        "better student's saved logits; needs --save_logits 1): prints the seg_crf table, writes "
+                        "<run>/segs/seg_preds/<infer_set>/<name>.png (+ the palette PNGs)")
     return p
 
 
 def main(argv=None):
-    """tools/eval_seg_voc.py:154-193 (`validate`) / tools/eval_seg_coco_ddp.py:142-248 up to the CRF stage: build the val
-    loader, load the reference-format checkpoint strictly, run the multi-scale + flip inference of both students, print the
-    score tables; under torch.distributed.run the COCO split is sharded round-robin over the ranks and the confusion
-    matrices are summed."""
+    """tools/eval_seg_voc.py:154-193 (`validate`) / tools/eval_seg_coco_ddp.py:205-256: build the val loader, load the
+    reference-format checkpoint strictly, run the multi-scale + flip inference of both students, print the score tables; with
+    --crf 1 go on to crf_proc; under torch.distributed.run the split is sharded round-robin over the ranks (for the CRF stage
+    too) and the confusion matrices are summed."""
     import os
     import numpy as np
     import torch.distributed as dist
@@ -173,6 +214,9 @@ def main(argv=None):
     if isinstance(args.scales, str):
         args.scales = [float(v) for v in args.scales.strip("()[] ").split(",")]
     args.scales = tuple(args.scales)
+    if args.crf and not args.save_logits:
+        raise SystemExit("--crf 1 reads the logits that --save_logits 1 writes (segs/logits/<infer_set>/branch{1,2}): "
+                         "run with --save_logits 1")
     local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(local)
@@ -209,10 +253,40 @@ def main(argv=None):
             s1, s2 = validate(model, loader, args, args.num_classes, voc.class_list, keep_logits=keep)
         else:
             s1, s2 = validate_coco(model, loader, args, args.num_classes, coco.class_list, keep_logits=keep)
-    if int(os.environ.get("RANK", "0")) == 0:
-        print({"Seg_1 mIoU": s1["miou"], "Seg_2 mIoU": s2["miou"],
-               "next": f"DenseCRF over {logits_dir}/branch{1 if s1['miou'] > s2['miou'] else 2} (reference: crf_proc, CPU)"})
-    return s1, s2
+    rank0 = int(os.environ.get("RANK", "0")) == 0
+    if not args.crf:
+        if rank0:
+            print({"Seg_1 mIoU": s1["miou"], "Seg_2 mIoU": s2["miou"],
+                   "next": f"DenseCRF over {logits_dir}/branch{1 if s1['miou'] > s2['miou'] else 2} (reference: crf_proc, CPU)"})
+        return s1, s2
+    # crf_proc (eval_seg_voc.py:185-188): the student with the higher mIoU; images sharded like the logits pass
+    branch = "branch1" if s1["miou"] > s2["miou"] else "branch2"
+    base = ds.dataset if world > 1 else ds
+    names = [str(n) for n in base.name_list][(dist.get_rank() if world > 1 else 0)::world]
+    test_set = "test" in args.infer_set
+    if is_voc:
+        image_path = lambda n: os.path.join(base.img_dir, n + ".jpg")
+        label_path = lambda n: os.path.join(base.label_dir, n + ".png")
+        rgb_dir = os.path.join(base_dir, "segs/seg_preds_rgb", args.infer_set)
+    else:
+        image_path = lambda n: base._paths(n)[0]
+        label_path = lambda n: base._paths(n)[1]
+        rgb_dir = os.path.join(base_dir, "segs", args.infer_set)
+
+    def label_of(name, image):
+        if test_set:
+            return image[:, :, 0]
+        return voc._read_label(label_path(name))
+
+    if rank0:
+        print("crf post-processing...")
+    with torch.no_grad():
+        crf = crf_proc(branch, names, image_path, label_of, logits_dir, os.path.join(base_dir, "segs/seg_preds", args.infer_set),
+                       rgb_dir, args.num_classes, dev)
+    if rank0:
+        print(format_tabs([crf], ["seg_crf"], cat_list=voc.class_list if is_voc else coco.class_list))
+        print({"Seg_1 mIoU": s1["miou"], "Seg_2 mIoU": s2["miou"], "seg_crf mIoU": crf["miou"]})
+    return s1, s2, crf
 
 
 if __name__ == "__main__":

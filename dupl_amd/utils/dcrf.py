@@ -1,0 +1,86 @@
+"""DenseCRF post-processing on the device (reference: utils/dcrf.py, which calls pydensecrf on the CPU): the same three
+callables with the same parameter names, defaults and constants.
+
+What runs here is the EXACT mean-field update of Kraehenbuehl & Koltun's fully connected CRF as pydensecrf.DenseCRF2D sets it up
+(Potts compatibility, DIAG_KERNEL, NORMALIZE_SYMMETRIC): every message is the dense sum over all pixel pairs (csrc/crf.hip,
+ops.dense_crf).  pydensecrf approximates that sum on a permutohedral lattice, so its output differs from this one by the
+lattice's approximation error.  No `seg_crf` figure from this code has been compared with one from pydensecrf (it is not
+installable where this package was built); the update is checked against a brute-force fp64 evaluation instead
+(tests/crf_ref.py, tests/test_crf_gpu.py).
+
+numpy in -> numpy out, as the reference; device tensors in -> device tensors out with no host round trip."""
+import numpy as np
+import torch
+
+from .. import ops
+
+
+def _is_np(*xs):
+    return not any(isinstance(x, torch.Tensor) for x in xs)
+
+
+def _dev(x, dtype):
+    if isinstance(x, torch.Tensor):
+        assert x.is_cuda, "device tensors (or numpy arrays) expected"
+        return x.to(dtype).contiguous()
+    return torch.from_numpy(np.ascontiguousarray(x)).to(dtype).cuda()
+
+
+def unary_from_softmax(probs):
+    """pydensecrf.utils.unary_from_softmax(sm, scale=None, clip=1e-5): -log(clip(p, 1e-5, 1)), (C,H,W) fp32."""
+    host = _is_np(probs)
+    U = ops.crf_unary(_dev(probs, torch.float32))
+    return U.cpu().numpy() if host else U
+
+
+def unary_from_labels(labels, n_labels, gt_prob, zero_unsure=False):
+    """pydensecrf.utils.unary_from_labels with zero_unsure=False (the only form utils/dcrf.py:32 uses): (n_labels,H,W) fp32."""
+    assert not zero_unsure, "zero_unsure=True is not used by the reference and not built"
+    host = _is_np(labels)
+    U = ops.crf_unary_labels(_dev(labels, torch.int64), n_labels, gt_prob)
+    return U.cpu().numpy() if host else U
+
+
+def _crf(img, unary, t, w_g, sxy_g, w_b, sxy_b, srgb_b):
+    return ops.dense_crf(unary, _dev(img, torch.uint8), t, w_g, sxy_g, w_b, sxy_b, srgb_b)
+
+
+def crf_inference(img, probs, t=10, scale_factor=1, labels=21):
+    """utils/dcrf.py:7-24: img (H,W,3) uint8, probs (labels,H,W) -> Q (labels,H,W)."""
+    host = _is_np(img, probs)
+    p = _dev(probs, torch.float32)
+    assert p.shape[0] == labels and tuple(p.shape[1:]) == tuple(img.shape[:2])
+    Q = _crf(img, ops.crf_unary(p), t, 3, 3 / scale_factor, 10, 80 / scale_factor, 13)
+    return Q.cpu().numpy() if host else Q
+
+
+def crf_inference_label(img, labels, t=10, n_labels=21, gt_prob=0.7):
+    """utils/dcrf.py:26-40: img (H,W,3) uint8, labels (H,W) in [0, n_labels) -> refined labels (H,W) int64."""
+    host = _is_np(img, labels)
+    lab = _dev(labels, torch.int64)
+    Q = _crf(img, ops.crf_unary_labels(lab, n_labels, gt_prob), t, 3, 3, 10, 50, 5)
+    out = ops.argmax_channels(Q[None])[0]
+    return out.cpu().numpy() if host else out
+
+
+class DenseCRF(object):
+    """utils/dcrf.py:42-69."""
+
+    def __init__(self, iter_max, pos_w, pos_xy_std, bi_w, bi_xy_std, bi_rgb_std):
+        self.iter_max = iter_max
+        self.pos_w = pos_w
+        self.pos_xy_std = pos_xy_std
+        self.bi_w = bi_w
+        self.bi_xy_std = bi_xy_std
+        self.bi_rgb_std = bi_rgb_std
+
+    def __call__(self, image, probmap):
+        host = _is_np(image, probmap)
+        Q = _crf(image, ops.crf_unary(_dev(probmap, torch.float32)), self.iter_max, self.pos_w, self.pos_xy_std, self.bi_w,
+                 self.bi_xy_std, self.bi_rgb_std)
+        return Q.cpu().numpy() if host else Q
+
+    def from_logits(self, image, logits):
+        """The same with the softmax of tools/eval_seg_voc.py:133 fused into the unary launch: logits (C,H,W) on the device."""
+        U = ops.crf_unary(_dev(logits, torch.float32), from_logits=True)
+        return _crf(image, U, self.iter_max, self.pos_w, self.pos_xy_std, self.bi_w, self.bi_xy_std, self.bi_rgb_std)

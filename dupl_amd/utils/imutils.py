@@ -1,4 +1,5 @@
-"""Input de-normalisation for PAR and the per-step strong augmentation (reference: utils/imutils.py:17-31,305-317)."""
+"""Input de-normalisation for PAR, the per-step strong augmentation and the VOC palette (reference: utils/imutils.py:12-31,
+41-59,305-317)."""
 import random
 
 import torch
@@ -9,6 +10,22 @@ from .._lib import lib as _L
 # randomaug.augment_list() (utils/randomaug.py:161-198): (op, minval, maxval)
 AUGMENT_LIST = (("AutoContrast", 0, 1), ("Equalize", 0, 1), ("Posterize", 0, 6), ("Color", 0.1, 1.9),
                 ("Contrast", 0.1, 1.9), ("Brightness", 0.1, 1.9), ("Sharpness", 0.1, 1.9))
+
+
+def colormap(N=256):
+    """The PASCAL VOC palette (N,3) uint8: bit k of the class index goes to bit 7 - k // 3 of channel k % 3."""
+    import numpy as np
+    idx = np.arange(N, dtype=np.int64)
+    cmap = np.zeros((N, 3), dtype=np.int64)
+    for bit in range(24):
+        cmap[:, bit % 3] |= ((idx >> bit) & 1) << (7 - bit // 3)
+    return cmap.astype(np.uint8)
+
+
+def encode_cmap(label):
+    """(H,W) class indices -> (H,W,3) uint8 palette colours (imutils.py:12-14)."""
+    import numpy as np
+    return colormap()[np.asarray(label).astype(np.int16), :]
 
 
 def denormalize_img(imgs=None, mean=None, std=None):

@@ -550,6 +550,41 @@ int dupl_photo_grayscale(uint8_t* img, int64_t n_px, dupl_stream_t s);
 /* transforms.GaussianBlur: img.filter(PIL.ImageFilter.GaussianBlur(radius)); tmp: H*W*3 bytes of scratch; result in img */
 int dupl_photo_gaussian_blur(uint8_t* img, uint8_t* tmp, int32_t H, int32_t W, float radius, dupl_stream_t s);
 
+/* ------------------------------------------------------------------ DenseCRF post-processing (csrc/crf.hip)
+ * utils/dcrf.py (pydensecrf.DenseCRF2D: Potts compatibility, DIAG_KERNEL, NORMALIZE_SYMMETRIC) as used by crf_proc of
+ * tools/eval_seg_voc.py:94-153 -- the EXACT mean-field update: every message is the dense sum over all pixel pairs that
+ * pydensecrf approximates on a permutohedral lattice.  Pixels row-major (i = y*W + x), N = H*W; img (H,W,3) uint8 interleaved;
+ * Q / unary / out (C,H,W) fp32.  Kernels k(i,j) = exp(-|f_i - f_j|^2 / 2) over ALL j (j = i included):
+ *   Gaussian  f = (x, y) / sxy;   bilateral  f = (x/sxy, y/sxy, r/srgb, g/srgb, b/srgb);   n_i = 1 / sqrt(sum_j k(i,j) + 1e-20).
+ * No fp32 atomics: results are bit-reproducible. */
+typedef struct dupl_crf_desc {
+    uint32_t struct_size;        /* sizeof(dupl_crf_desc), checked */
+    int32_t C, H, W;             /* >= 1 each */
+    int32_t T;                   /* dupl_dense_crf: mean-field iterations (>= 0) */
+    int32_t reserved0;
+    const uint8_t* img;          /* dupl_crf_message: NULL = Gaussian kernel; dupl_dense_crf: required */
+    const float* Q;              /* dupl_crf_message: input (C,H,W); NULL = write n (N floats) to `out` */
+    const float* norm;           /* dupl_crf_message: n (N floats) or NULL (no normalisation, n = 1) */
+    const float* unary;          /* dupl_dense_crf: U (C,H,W) */
+    float* out;                  /* dupl_crf_message: M(Q) (C,H,W) (or n); dupl_dense_crf: Q after T iterations (C,H,W) */
+    float* workspace;            /* dupl_dense_crf: >= (2 + 2*C) * N floats of scratch */
+    int64_t workspace_bytes;
+    float sxy, srgb;             /* dupl_crf_message: the kernel's standard deviations (srgb unused without img) */
+    float w_g, sxy_g;            /* dupl_dense_crf: addPairwiseGaussian(sxy, compat) */
+    float w_b, sxy_b, srgb_b;    /* dupl_dense_crf: addPairwiseBilateral(sxy, srgb, compat) */
+    int32_t reserved1;
+} dupl_crf_desc;
+/* one application of one kernel: out[c,i] = n_i * sum_j k(i,j) * n_j * Q[c,j] */
+int dupl_crf_message(const dupl_crf_desc* d, dupl_stream_t stream);
+/* Q^0 = softmax_c(-U); T times Q = softmax_c(-U + w_g M_g(Q) + w_b M_b(Q)); per iteration one launch per kernel + one fused
+ * energy / softmax launch (DenseCRF2D.inference(T) of utils/dcrf.py:22,38,66) */
+int dupl_dense_crf(const dupl_crf_desc* d, dupl_stream_t stream);
+/* pydensecrf.utils.unary_from_softmax (utils/dcrf.py:14,54): U = -log(clip(p, 1e-5, 1)), in / U (C,N).  mode 0: in = p;
+ * mode 1: in = logits, p = softmax_c(in) first (F.softmax of tools/eval_seg_voc.py:133 fused) */
+int dupl_crf_unary(const float* in, float* U, int32_t C, int64_t N, int32_t mode, dupl_stream_t s);
+/* pydensecrf.utils.unary_from_labels(labels, C, gt_prob, zero_unsure=False) (utils/dcrf.py:32): labels (N) int64 in [0,C) */
+int dupl_crf_unary_labels(const int64_t* labels, float* U, int32_t C, int64_t N, double gt_prob, dupl_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

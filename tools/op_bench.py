@@ -1,5 +1,6 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd]"""
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf]
+`crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81."""
 import gc
 import sys
 
@@ -23,10 +24,35 @@ def timeit(fn, n=200, warm=20):
     return a.elapsed_time(b) * 1e3 / n
 
 
+def crf_bench(dev, g):
+    """The full 10-iteration CRF of eval_seg --crf 1, one bilateral message launch, one Gaussian (stencil) launch, the two
+    normaliser launches and the fused softmax, per image size.  pairs/s = N^2 / (time of one bilateral launch)."""
+    for H, W, C in ((375, 500, 21), (480, 640, 81)):
+        N = H * W
+        img = torch.randint(0, 256, (H, W, 3), generator=g, dtype=torch.uint8).to(dev)
+        Q = torch.softmax(torch.randn(C, H, W, generator=g) * 2, 0).to(dev)
+        U = ops.crf_unary(Q)
+        nb, ng = ops.crf_norm(img, H, W, 121.0, 5.0), ops.crf_norm(None, H, W, 1.0, device=dev)
+        t_b = timeit(lambda: ops.crf_message(img, Q, 121.0, 5.0, normalize=nb), n=5, warm=1)
+        t_g = timeit(lambda: ops.crf_message(None, Q, 1.0, normalize=ng), n=20, warm=2)
+        t_nb = timeit(lambda: ops.crf_norm(img, H, W, 121.0, 5.0), n=5, warm=1)
+        t_u = timeit(lambda: ops.crf_unary(Q, from_logits=True), n=20, warm=2)
+        t_all = timeit(lambda: ops.dense_crf(U, img, 10, 1.0, 1.0, 4.0, 121.0, 5.0), n=2, warm=1)
+        chunks = (C + 31) // 32
+        print(f"crf {H}x{W}x{C}: dense_crf T=10 {t_all / 1e3:.1f} ms/image; bilateral message {t_b / 1e3:.2f} ms = "
+              f"{N * N / t_b / 1e6:.2f} Tpairs/s ({chunks} channel chunk(s): {chunks * N * N / t_b / 1e6:.2f} T kernel evaluations/s, "
+              f"{2 * 32 * chunks * N * N / t_b / 1e6:.1f} TFLOP/s of MFMA, 32 channel rows per chunk); bilateral normaliser {t_nb / 1e3:.2f} ms; Gaussian stencil message "
+              f"{t_g:.0f} us; unary from logits {t_u:.0f} us")
+
+
 def main():
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
+    if "crf" in which:
+        crf_bench(dev, g)
+        if which == {"crf"}:
+            return
     rows, D = 3140, 768
     x = torch.randn(rows, D, generator=g).to(dev)
     dy = (torch.randn(rows, D, generator=g) * 1e-5).to(dev)

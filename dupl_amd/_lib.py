@@ -91,6 +91,21 @@ class CrfDesc(ctypes.Structure):
         self.struct_size = ctypes.sizeof(CrfDesc)
 
 
+class CamEvalDesc(ctypes.Structure):
+    """Mirror of `dupl_cam_eval_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("B", ctypes.c_int32), ("C", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+        ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("T", ctypes.c_int32), ("num_classes", ctypes.c_int32),
+        ("label_at", ctypes.c_int32), ("impl", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+        ("cam", ctypes.c_void_p), ("cls_label", ctypes.c_void_p), ("thr", ctypes.c_void_p), ("gt", ctypes.c_void_p),
+        ("hist", ctypes.c_void_p), ("label_out", ctypes.c_void_p), ("value_out", ctypes.c_void_p),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(CamEvalDesc)
+
+
 GEMM_A_MCONTIG, GEMM_B_NCONTIG, GEMM_GELU, GEMM_ACCUM = 1, 2, 4, 8
 GEMM_MUL_DGELU, GEMM_RELU, GEMM_MUL_RELUMASK, GEMM_ABS, GEMM_STORE_PRE = 16, 32, 64, 128, 256
 
@@ -110,6 +125,7 @@ class AttnSeg(ctypes.Structure):
 ATTN_SEGS_MAX = 4             # DUPL_ATTN_SEGS_MAX
 SPLIT_MULTI_MAX = 16
 GEMM16_GROUP_MAX = 8          # DUPL_GEMM16_GROUP_MAX
+CAM_EVAL_MAX_T, CAM_EVAL_MAX_C = 64, 255      # DUPL_CAM_EVAL_MAX_T, DUPL_CAM_EVAL_MAX_C
 
 _PROTO = re.compile(r"^\s*int\s+(dupl_\w+)\s*\(([^;{]*)\)\s*;", re.M | re.S)
 
@@ -126,6 +142,8 @@ def _ctype(decl: str):
         return ctypes.POINTER(GemmDesc)
     if "dupl_crf_desc" in d:
         return ctypes.POINTER(CrfDesc)
+    if "dupl_cam_eval_desc" in d:
+        return ctypes.POINTER(CamEvalDesc)
     if "*" in d or d.startswith("dupl_stream_t"):
         return ctypes.c_void_p
     base = d.replace("const", "").split()

@@ -960,3 +960,97 @@ def crf_unary_labels(labels: Tensor, n_labels: int, gt_prob: float) -> Tensor:
     U = torch.empty((int(n_labels),) + tuple(labels.shape), device=labels.device, dtype=torch.float32)
     L().dupl_crf_unary_labels(labels.data_ptr(), U.data_ptr(), int(n_labels), labels.numel(), float(gt_prob), _stream())
     return U
+
+
+# ------------------------------------------------------------------------------------------ offline CAM inference (csrc/cam_eval.hip)
+_JET = {"red": ((0., 0.), (.35, 0.), (.66, 1.), (.89, 1.), (1., .5)),
+        "green": ((0., 0.), (.125, 0.), (.375, 1.), (.64, 1.), (.91, 0.), (1., 0.)),
+        "blue": ((0., .5), (.11, 1.), (.34, 1.), (.65, 0.), (1., 0.))}
+
+
+def jet_lut(N: int = 256) -> np.ndarray:
+    """matplotlib's `jet` as an (N,3) float64 table, from its segment data through the arithmetic of
+    matplotlib.colors._create_lookup_table (gamma 1) -- the table cam_overlay_kernel builds; no matplotlib needed."""
+    out = np.empty((N, 3), dtype=np.float64)
+    xind = (N - 1) * np.linspace(0, 1, N)
+    for c, key in enumerate(("red", "green", "blue")):
+        x = np.array([p[0] for p in _JET[key]], dtype=np.float64) * (N - 1)
+        y = np.array([p[1] for p in _JET[key]], dtype=np.float64)
+        ind = np.searchsorted(x, xind)[1:-1]
+        dist = (xind[1:-1] - x[ind - 1]) / (x[ind] - x[ind - 1])
+        out[:, c] = np.clip(np.concatenate([[y[0]], dist * (y[ind] - y[ind - 1]) + y[ind - 1], [y[-1]]]), 0.0, 1.0)
+    return out
+
+
+def check_thresholds(thresholds) -> np.ndarray:
+    """The thresholds of cam_eval as a float32 array; ValueError unless 1 <= T <= 64, ascending, all in [0, 1]."""
+    thr = np.asarray(thresholds, dtype=np.float32).reshape(-1)
+    if not 1 <= thr.size <= _lib.CAM_EVAL_MAX_T:
+        raise ValueError(f"cam_eval takes 1 .. {_lib.CAM_EVAL_MAX_T} thresholds, got {thr.size}")
+    if not bool(np.all((thr >= 0) & (thr <= 1))) or bool(np.any(np.diff(thr) < 0)):
+        raise ValueError(f"cam_eval thresholds must be ascending and lie in [0, 1]: {thr.tolist()}")
+    return thr
+
+
+def sweep_bins_to_hists(bins, slot_pred, T: int) -> np.ndarray:
+    """The identity behind cam_eval's histogram, on the host: bins (nc, S, T+1) counts of (gt, class slot, k), where
+    k = #{t : thr[t] < v} for ascending thresholds, and slot_pred (S,) the label of a slot when it is foreground
+    -> (T, nc, nc) confusion matrices: a pixel predicts slot_pred[s] at the thresholds t < k and 0 at the others."""
+    bins = np.asarray(bins, dtype=np.int64)
+    nc, S, T1 = bins.shape
+    assert T1 == T + 1 and len(slot_pred) == S
+    suffix = np.cumsum(bins[:, :, ::-1], axis=2)[:, :, ::-1]          # suffix[g, s, k] = sum over k' >= k
+    hist = np.zeros((T, nc, nc), dtype=np.int64)
+    for t in range(T):
+        fg = suffix[:, :, t + 1]
+        for s in range(S):
+            hist[t, :, int(slot_pred[s])] += fg[:, s]
+        hist[t, :, 0] += (suffix[:, :, 0] - fg).sum(1)
+    return hist
+
+
+def cam_eval(cam: Tensor, cls_label: Tensor, out_size, thresholds, gt: Optional[Tensor] = None, hist: Optional[Tensor] = None,
+             label_at: Optional[int] = None, want_value: bool = False, impl: int = 0):
+    """One pass over the (H,W) = out_size grid for cam (B,C,h,w), cls_label (B,C): per pixel v / a = max / argmax over the channels
+    of cls_label * bilinear(cam) (align_corners False; only the classes present are sampled), then
+      hist (T,nc,nc) int64 += evaluate._fast_hist(gt, v <= thr[t] ? 0 : a + 1) for every t (needs gt (B,H,W) int64),
+      label (B,H,W) uint8 at thresholds[label_at] (cam_helper.cam_to_label(..., bkg_thre) on the resized CAMs),
+      value (B,H,W) fp32 = v (the max of get_valid_cam over the channels).
+    Returns (label or None, value or None); hist is updated in place.  impl 1 forces the global-atomics histogram."""
+    B, C, h, w = cam.shape
+    H, W = int(out_size[0]), int(out_size[1])
+    cam = _chk(cam.contiguous())
+    cls_label = _chk(cls_label.contiguous().float())
+    assert tuple(cls_label.shape) == (B, C)
+    thr = check_thresholds(thresholds)
+    T = int(thr.size)
+    dev = cam.device
+    nc = 0
+    if hist is not None:
+        assert gt is not None, "cam_eval: hist needs gt"
+        assert hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and hist.dim() == 3
+        assert hist.shape[0] == T and hist.shape[1] == hist.shape[2], f"hist must be (T, nc, nc), got {tuple(hist.shape)}"
+        nc = int(hist.shape[1])
+        assert gt.is_cuda and gt.dtype == torch.int64 and tuple(gt.shape) == (B, H, W)
+        gt = gt.contiguous()
+    label = torch.empty((B, H, W), device=dev, dtype=torch.uint8) if label_at is not None else None
+    value = torch.empty((B, H, W), device=dev, dtype=torch.float32) if want_value else None
+    d = _lib.CamEvalDesc(B=B, C=C, h=h, w=w, H=H, W=W, T=T, num_classes=nc, label_at=int(label_at) if label_at is not None else 0,
+                         impl=int(impl), cam=cam.data_ptr(), cls_label=cls_label.data_ptr(), thr=thr.ctypes.data,
+                         gt=_p(gt) if hist is not None else None, hist=_p(hist), label_out=_p(label), value_out=_p(value))
+    L().dupl_cam_eval(ctypes.byref(d), _stream())
+    return label, value
+
+
+def cam_overlay(value: Tensor, inputs: Optional[Tensor] = None, alpha: float = 0.6) -> Tensor:
+    """value (B,H,W) fp32 in [0,1], inputs (B,3,H,W) normalised images or None -> (B,H,W,3) uint8:
+    trunc(alpha * 255 * jet(value) + (1 - alpha) * denormalize_img(inputs)) in float64 (tools/infer_cam_voc.py:81-88);
+    without inputs the truncated jet colour alone."""
+    B, H, W = value.shape
+    value = _chk(value.contiguous())
+    if inputs is not None:
+        inputs = _chk(inputs.contiguous())
+        assert tuple(inputs.shape) == (B, 3, H, W)
+    out = torch.empty((B, H, W, 3), device=value.device, dtype=torch.uint8)
+    L().dupl_cam_overlay(value.data_ptr(), _p(inputs), out.data_ptr(), B, H, W, float(alpha), None, _stream())
+    return out

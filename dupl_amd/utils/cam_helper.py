@@ -1,7 +1,8 @@
 """CAM / pseudo-label helpers -- the reference's utils/cam_helper.py (superset of utils/camutils.py) API on
 the HIP kernels: multi_scale_cam2[_siamese], cam_to_label[_dynamic_cls], label_to_aff_mask,
 refine_cams_with_bkg_v2, refine_cams_with_dynamic_thres.  Signatures, return order and dtypes follow the
-reference (cam_helper.py:8-55,164-204,323-440); inputs must live on the GPU.
+reference (cam_helper.py:8-55,164-204,323-440); inputs must live on the GPU.  get_valid_cam, ignore_img_box and
+cam_to_roi_mask2 (cam_helper.py:58-87) are plain torch expressions and take tensors on any device.
 """
 from typing import Optional, Sequence
 
@@ -196,3 +197,25 @@ def refine_cams_with_dynamic_thres(ref_mod=None, images=None, cams=None, cls_lab
                                    low_thre=None, ignore_index=False, img_box=None, down_scale=2, aff=None):
     """cam_helper.py:386-431: high threshold given as a (b,1,H,W) map.  aff: as in refine_cams_with_bkg_v2."""
     return _refine(ref_mod, images, cams, cls_labels, None, high_thre_map, low_thre, ignore_index, img_box, down_scale, aff=aff)
+
+
+def get_valid_cam(cam, cls_label):
+    """cam_helper.py:72-78: the CAMs with the channels of absent classes zeroed, cls_label (b,C) * cam (b,C,h,w)."""
+    return cls_label[:, :, None, None] * cam
+
+
+def ignore_img_box(label, img_box, ignore_index):
+    """cam_helper.py:81-87: `label` inside each image's box (y0, y1, x0, x1), ignore_index outside."""
+    out = torch.full_like(label, ignore_index)
+    for i, (y0, y1, x0, x1) in enumerate(img_box):
+        out[i, y0:y1, x0:x1] = label[i, y0:y1, x0:x1]
+    return out
+
+
+def cam_to_roi_mask2(cam, cls_label, hig_thre=None, low_thre=None):
+    """cam_helper.py:58-69 -> (b,h,w) int16: 0 where the max valid CAM is <= low_thre, 2 where it is >= hig_thre, else 1."""
+    value = get_valid_cam(cam, cls_label).max(dim=1)[0]
+    roi = torch.ones_like(value, dtype=torch.int16)
+    roi[value <= low_thre] = 0
+    roi[value >= hig_thre] = 2
+    return roi

@@ -69,3 +69,27 @@ class ConfusionMatrix:
 
     def scores(self):
         return scores_from_hist(self.hist.cpu().numpy())
+
+
+class ThresholdSweep:
+    """Device-resident (T, nc, nc) int64 histograms, one confusion matrix per background threshold, filled by the fused pass
+    ops.cam_eval (csrc/cam_eval.hip): T thresholds cost the same pass over the label grid as one."""
+
+    def __init__(self, num_classes, thresholds, device):
+        self.num_classes = int(num_classes)
+        self.thresholds = [float(t) for t in ops.check_thresholds(thresholds)]
+        self.hist = torch.zeros((len(self.thresholds), self.num_classes, self.num_classes), device=device, dtype=torch.int64)
+
+    def update(self, cam, cls_label, gt, label_at=None, want_value=False):
+        """cam (B,C,h,w), cls_label (B,C), gt (B,H,W) int64 -> (label at thresholds[label_at] or None, max value or None)."""
+        return ops.cam_eval(cam, cls_label, gt.shape[-2:], self.thresholds, gt=gt, hist=self.hist, label_at=label_at,
+                            want_value=want_value)
+
+    def scores(self):
+        return [scores_from_hist(h) for h in self.hist.cpu().numpy()]
+
+    def best(self):
+        """(threshold, score dict) of the highest mIoU; the lowest such threshold on equal mIoU."""
+        sc = self.scores()
+        i = max(range(len(sc)), key=lambda k: (sc[k]["miou"], -k))
+        return self.thresholds[i], sc[i]

@@ -585,6 +585,38 @@ int dupl_crf_unary(const float* in, float* U, int32_t C, int64_t N, int32_t mode
 /* pydensecrf.utils.unary_from_labels(labels, C, gt_prob, zero_unsure=False) (utils/dcrf.py:32): labels (N) int64 in [0,C) */
 int dupl_crf_unary_labels(const int64_t* labels, float* U, int32_t C, int64_t N, double gt_prob, dupl_stream_t s);
 
+/* ------------------------------------------------------------------ offline CAM inference (csrc/cam_eval.hip)
+ * The tail of tools/infer_cam_voc.py:69-92 after the 448^2 multi-scale CAMs, in one pass over the (H,W) label grid: bilinear
+ * up-sampling (align_corners False) of the classes present in the image, max / argmax over the channels (absent channels count
+ * as 0, first maximum wins: valid_cam.max(dim=1) of utils/cam_helper.py:12-16), the label map `v <= thr ? 0 : argmax + 1`, and the
+ * confusion matrices of evaluate._fast_hist for T background thresholds at once.  With thr ascending a pixel is foreground at
+ * threshold t exactly when t < k, k = #{t : thr[t] < v}: one histogram over (gt, class, k) gives all T matrices. */
+#define DUPL_CAM_EVAL_MAX_T 64
+#define DUPL_CAM_EVAL_MAX_C 255
+typedef struct dupl_cam_eval_desc {
+    uint32_t struct_size;        /* sizeof(dupl_cam_eval_desc), checked */
+    int32_t B, C, h, w;          /* cam (B,C,h,w) fp32, min-max normalised; 1 <= C <= DUPL_CAM_EVAL_MAX_C */
+    int32_t H, W;                /* output grid */
+    int32_t T;                   /* thresholds, 1 .. DUPL_CAM_EVAL_MAX_T */
+    int32_t num_classes;         /* nc of hist (>= C + 1); unused without hist */
+    int32_t label_at;            /* threshold index of label_out, 0 .. T-1; unused without label_out */
+    int32_t impl;                /* 0: bins privatised in LDS where they fit; 1: global atomics always (A/B tests) */
+    int32_t reserved0;
+    const float* cam;
+    const float* cls_label;      /* (B,C) fp32; a class is present when its entry is != 0 */
+    const float* thr;            /* HOST array of T thresholds: ascending, each in [0, 1] (validated here) */
+    const int64_t* gt;           /* (B,H,W) ground truth; required with hist; values outside [0, nc) are skipped */
+    int64_t* hist;               /* (T,nc,nc), hist[t][gt][pred] += counts; or NULL */
+    uint8_t* label_out;          /* (B,H,W) label map at thr[label_at]; or NULL */
+    float* value_out;            /* (B,H,W) the maximum v; or NULL */
+} dupl_cam_eval_desc;
+int dupl_cam_eval(const dupl_cam_eval_desc* d, dupl_stream_t stream);
+/* The overlay of tools/infer_cam_voc.py:81-88: out (B,H,W,3) uint8 = trunc(alpha * 255 * jet(value) + (1 - alpha) * denorm(img)) in
+ * float64, jet = matplotlib's 256-entry table at index min(int(value * 256), 255), denorm = the uint8 rule of dupl_denormalize_img
+ * (mean_std: 6 host floats or NULL).  value (B,H,W) fp32; img (B,3,H,W) normalised, or NULL: the truncated colour alone. */
+int dupl_cam_overlay(const float* value, const float* img, uint8_t* out, int32_t B, int32_t H, int32_t W, double alpha,
+                     const float* mean_std, dupl_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,7 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf]
-`crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81."""
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval]
+`crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81.
+`cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces."""
 import gc
 import sys
 
@@ -45,10 +46,61 @@ def crf_bench(dev, g):
               f"{t_g:.0f} us; unary from logits {t_u:.0f} us")
 
 
+def cam_eval_bench(dev, g):
+    """ops.cam_eval (histograms of T thresholds + label map + value, one launch) against the composed path of the ops it fuses:
+    resize_bilinear, then per threshold cam_to_label and ConfusionMatrix.update; 448^2 CAMs, batch 1.  Bytes of the fused pass:
+    8 (gt) + 4 (value) + 1 (label) per pixel plus the 448^2 floats of every class present, read once."""
+    from dupl_amd.utils import cam_helper, evaluate
+    for H, W, C, K in ((375, 500, 20, 2), (480, 640, 80, 6), (480, 640, 80, 20)):       # K = 20 at T = 19: two threshold chunks
+        nc = C + 1
+        low = torch.rand((1, C, 28, 28), generator=g)
+        cam = torch.nn.functional.interpolate(low, size=(448, 448), mode="bilinear", align_corners=False).to(dev).contiguous()
+        cls = torch.zeros((1, C))
+        cls[0, torch.randperm(C, generator=g)[:K]] = 1.0
+        # ground truth as in a data set: blobs of background and the classes present, some 255
+        ids = torch.cat([torch.zeros(1), torch.nonzero(cls[0])[:, 0] + 1, torch.tensor([255.0])])
+        gt = ids[torch.randint(0, ids.numel(), (1, 1, 6, 8), generator=g)]
+        gt = torch.nn.functional.interpolate(gt, size=(H, W), mode="nearest")[0].long().to(dev)
+        cls = cls.to(dev)
+        for thr in ([0.5], [0.05 + 0.05 * i for i in range(19)]):
+            T = len(thr)
+            hist = torch.zeros((T, nc, nc), device=dev, dtype=torch.int64)
+            cms = [evaluate.ConfusionMatrix(nc, dev) for _ in thr]
+
+            def composed():
+                rc = ops.resize_bilinear(cam, H, W)
+                for t, cm in zip(thr, cms):
+                    cm.update(gt, cam_helper.cam_to_label(rc, cls, bkg_thre=t))
+
+            t_c = timeit(composed, n=50, warm=5)
+            t_f = timeit(lambda: ops.cam_eval(cam, cls, (H, W), thr, gt=gt, hist=hist, label_at=T // 2, want_value=True), n=200)
+            t_g = timeit(lambda: ops.cam_eval(cam, cls, (H, W), thr, gt=gt, hist=hist, label_at=T // 2, want_value=True, impl=1), n=50,
+                         warm=5)
+            # the launch alone: descriptor and outputs built once, so the host adds one ctypes call per launch
+            import ctypes
+            import numpy as np
+            from dupl_amd import _lib
+            label = torch.empty((1, H, W), device=dev, dtype=torch.uint8)
+            value = torch.empty((1, H, W), device=dev, dtype=torch.float32)
+            arr = np.asarray(thr, dtype=np.float32)
+            d = _lib.CamEvalDesc(B=1, C=C, h=448, w=448, H=H, W=W, T=T, num_classes=nc, label_at=T // 2, cam=cam.data_ptr(),
+                                 cls_label=cls.data_ptr(), thr=arr.ctypes.data, gt=gt.data_ptr(), hist=hist.data_ptr(),
+                                 label_out=label.data_ptr(), value_out=value.data_ptr())
+            fn, ref, st = ops.L().dupl_cam_eval.raw, ctypes.byref(d), ops._stream()
+            t_k = timeit(lambda: fn(ref, st), n=500)
+            nbytes = H * W * 13 + K * 448 * 448 * 4
+            print(f"cam_eval {H}x{W} C={C} K={K} T={T}: ops.cam_eval {t_f:.1f} us, launch alone {t_k:.1f} us ({nbytes / t_k / 1e6:.3f} TB/s); "
+                  f"composed {t_c:.1f} us ({t_c / t_f:.1f}x ops.cam_eval); with the global-atomics histogram {t_g:.1f} us")
+
+
 def main():
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
+    if "cam_eval" in which:
+        cam_eval_bench(dev, g)
+        if which <= {"cam_eval", "crf"} and "crf" not in which:
+            return
     if "crf" in which:
         crf_bench(dev, g)
         if which == {"crf"}:

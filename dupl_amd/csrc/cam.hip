@@ -36,7 +36,10 @@ __device__ __forceinline__ float bil_blend(float hy, float ly, float lx, float a
 }
 
 // max(a, b, 0) in ONE instruction (fmaxf(fmaxf(a, b), 0.f) costs three more for input canonicalisation in IEEE mode); used by both
-// fusion kernels, so they agree bit for bit whatever the inputs
+// fusion kernels, so they agree bit for bit whatever the inputs.  Non-finite inputs: v_max3_f32 returns the largest NON-NaN operand,
+// so a NaN up-sampled value (any of its four taps NaN) is dropped -- both NaN gives 0 -- where torch's max / relu would propagate
+// it: the fused CAM launders NaN logits to the other image's value or 0, identically in both kernels
+// (tests/test_glue_kernels_gpu.py::test_cam_fuse_nan_contract).
 __device__ __forceinline__ float max3_relu(float a, float b) {
     float r;
     asm("v_max3_f32 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(b));

@@ -103,6 +103,9 @@ __global__ void assemble_tokens_bwd_kernel(const float* __restrict__ dtok, float
 }
 
 // global max pool over patch rows 1..n of tokens [B][1+n][D]; first index wins ties (torch semantics)
+// Non-finite columns follow torch.max too: a NaN anywhere in the column gives NaN with the index of the FIRST NaN, an all -inf
+// column gives -inf with index 0.  The index is therefore always in [0, n) and gmp_bwd's scatter stays inside dtokens (it was
+// INT_MAX, a wild store, when no row ever compared greater than the -inf start).
 // 16 row groups x 64 columns per block, 4 independent loads in flight per thread: the 48-block launch is latency-bound (it was
 // 83-187 us with 4 row groups and one dependent load at a time)
 __global__ __launch_bounds__(1024) void gmp_fwd_kernel(const float* __restrict__ tok, float* __restrict__ out,
@@ -113,21 +116,21 @@ __global__ __launch_bounds__(1024) void gmp_fwd_kernel(const float* __restrict__
     const int cl = threadIdx.x & 63, rg = threadIdx.x >> 6;
     const int col = blockIdx.x * 64 + cl, b = blockIdx.y;
     float best = -INFINITY;
-    int bi = 0x7fffffff;
+    int bi = rg < n ? rg : 0x7fffffff;   // a group without rows keeps INT_MAX and never wins the merge (group 0 has row 0)
     if (col < D) {
         const float* base = tok + ((long)b * (n + 1) + 1) * D + col;
         int i = rg;
         for (; i + 3 * RG < n; i += 4 * RG) {
             const float v0 = base[(long)i * D], v1 = base[(long)(i + RG) * D], v2 = base[(long)(i + 2 * RG) * D],
                         v3 = base[(long)(i + 3 * RG) * D];
-            if (v0 > best) { best = v0; bi = i; }
-            if (v1 > best) { best = v1; bi = i + RG; }
-            if (v2 > best) { best = v2; bi = i + 2 * RG; }
-            if (v3 > best) { best = v3; bi = i + 3 * RG; }
+            if (v0 > best || (v0 != v0 && best == best)) { best = v0; bi = i; }
+            if (v1 > best || (v1 != v1 && best == best)) { best = v1; bi = i + RG; }
+            if (v2 > best || (v2 != v2 && best == best)) { best = v2; bi = i + 2 * RG; }
+            if (v3 > best || (v3 != v3 && best == best)) { best = v3; bi = i + 3 * RG; }
         }
         for (; i < n; i += RG) {
             const float v = base[(long)i * D];
-            if (v > best) { best = v; bi = i; }
+            if (v > best || (v != v && best == best)) { best = v; bi = i; }
         }
     }
     sv[rg][cl] = best;
@@ -138,7 +141,9 @@ __global__ __launch_bounds__(1024) void gmp_fwd_kernel(const float* __restrict__
         for (int g = 1; g < RG; ++g) {
             const float v = sv[g][cl];
             const int i = si[g][cl];
-            if (v > best || (v == best && i < bi)) { best = v; bi = i; }
+            // NaN beats every number, the lower index wins among NaNs and among equal numbers
+            const bool take = (v != v) ? (best == best || i < bi) : (best == best && (v > best || (v == best && i < bi)));
+            if (take) { best = v; bi = i; }
         }
         out[(long)b * D + col] = best;
         idx[(long)b * D + col] = bi;

@@ -51,7 +51,13 @@ def test_confusion_f1_argmax_kernels(dev):
     logits = torch.randn(3, 21, 13, 17)
     up = F.interpolate(logits, size=(75, 100), mode="bilinear", align_corners=False)
     got = ops.upsample_argmax(logits.to(dev), 75, 100).cpu()
-    assert int((got != up.argmax(1)).sum()) <= 2
+    # a pixel may differ from the float64 argmax only where the float64 top-1 - top-2 margin is within twice what a correct fp32
+    # bilinear may be off (tests/glue_ref.py), and such pixels are at most 0.1 % of the map
+    import glue_ref
+    arg64, margin, bound = glue_ref.upsample_argmax64(logits, 75, 100)
+    excusable = margin <= 2.0 * bound
+    assert not bool(((got != arg64) & ~excusable).any())
+    assert int(excusable.sum()) <= 1e-3 * excusable.numel()
     assert torch.equal(ops.argmax_channels(up.to(dev)).cpu(), up.argmax(1))
     from sklearn.metrics import f1_score
     cls = torch.randn(5, 20)

@@ -172,6 +172,7 @@ def test_token_plumbing(dev):
     mx, idx = ops.gmp_fwd(tok, B, n, D)
     rm, ri = reft[:, 1:].max(dim=1)
     assert relerr(mx, rm) < 3e-6
+    assert torch.equal(idx.cpu().long(), ri)
     nchw = ops.tokens_to_nchw(tok, B, n, D, h, w)
     assert relerr(nchw, reft[:, 1:].transpose(1, 2).reshape(B, D, h, w)) < 3e-6
     dt = torch.zeros_like(tok)

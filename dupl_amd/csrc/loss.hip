@@ -433,7 +433,8 @@ __global__ __launch_bounds__(64 * CS_RG) void cos_sim_fwd_kernel(const float* __
     }
 }
 
-// gradient wrt `bb` only: d cos / d b_i = a_i/(na*nb) - cos * b_i / nb^2  (norms above eps)
+// gradient wrt `bb` only: d cos / d b_i = a_i/(na*nb) - cos * b_i / nb^2 with the clamped norms; where |b| <= eps the clamp has zero
+// slope -- the derivative of the function computed -- and the second term is dropped.  Columns with |b| > eps: unchanged arithmetic.
 __global__ void cos_sim_bwd_kernel(const float* __restrict__ a, const float* __restrict__ bb, const float* __restrict__ stats,
                                    const float* __restrict__ g, float gmul, float* __restrict__ db, int B, int n, int c, long ld,
                                    long ims, float eps, int accumulate) {
@@ -447,7 +448,7 @@ __global__ void cos_sim_bwd_kernel(const float* __restrict__ a, const float* __r
         const float cs = st[0] / (na * nb);
         const long off = img * ims + (long)t * ld + col;
         const float gv = g[0] * gmul;
-        const float v = gv * (a[off] / (na * nb) - cs * bb[off] / (nb * nb));
+        const float v = sqrtf(st[2]) > eps ? gv * (a[off] / (na * nb) - cs * bb[off] / (nb * nb)) : gv * (a[off] / (na * nb));
         db[off] = accumulate ? db[off] + v : v;
     }
 }
@@ -500,7 +501,11 @@ struct loss_total_args {
     float weight[DUPL_LOSS_TERMS_MAX];
     int n, ng;
 };
+// __fmul_rn / __fadd_rn are plain * and + in this compiler's headers, inlined with the default contraction: w_g G_g + total became
+// ONE fma (one rounding instead of the torch expression's two; the total was off by an ulp or two whenever a product was inexact).
+// The arithmetic is written out under contract(off) instead.
 __global__ void loss_total_kernel(const loss_total_args a, float* __restrict__ tot, float* __restrict__ gsums) {
+#pragma clang fp contract(off)
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     float total = 0.f;
     for (int g = 0; g < a.ng; ++g) {
@@ -509,13 +514,13 @@ __global__ void loss_total_kernel(const loss_total_args a, float* __restrict__ t
         for (int i = 0; i < a.n; ++i) {
             if (a.group[i] != g) continue;
             float v = *a.term[i];
-            if (a.add[i] != 0.f) v = __fadd_rn(a.add[i], v);
-            G = first ? v : __fadd_rn(G, v);
+            if (a.add[i] != 0.f) v = a.add[i] + v;
+            G = first ? v : G + v;
             first = false;
         }
         if (gsums) gsums[g] = G;
-        const float wg = __fmul_rn(a.weight[g], G);
-        total = g == 0 ? wg : __fadd_rn(total, wg);
+        const float wg = a.weight[g] * G;
+        total = g == 0 ? wg : total + wg;
     }
     tot[0] = total;
 }
@@ -605,7 +610,8 @@ extern "C" int dupl_seg_ce_map(const float* logits, const void* label, int32_t i
 extern "C" int dupl_seg_loss_bwd(const float* logits, const void* label, int32_t is_i64, int32_t ignore_index, const float* sums,
                                  const float* gscale, float* dlogits, int32_t b, int32_t C1, int32_t h, int32_t w, int32_t H,
                                  int32_t W, int32_t flip, int32_t balanced, int32_t deterministic, dupl_stream_t s) {
-    if (!logits || !label || !sums || !gscale || !dlogits || b <= 0 || C1 <= 0 || H < h || W < w) return DUPL_ERR_ARG;
+    if (!logits || !label || !sums || !gscale || !dlogits || b <= 0 || C1 <= 0 || h <= 0 || w <= 0 || H < h || W < w)
+        return DUPL_ERR_ARG;
     if (deterministic) {
         int nthr = 256;                                        // <= 64 KB of dynamic LDS: [threads][C1 + 1] floats
         while (nthr > 64 && (size_t)nthr * (C1 + 1) * sizeof(float) > 64 * 1024) nthr >>= 1;
@@ -624,7 +630,8 @@ extern "C" int dupl_seg_loss_bwd(const float* logits, const void* label, int32_t
 extern "C" int dupl_seg_pseudo_label(const float* logits, const float* other_label, int32_t ignore_index, float conf_thr,
                                      int64_t* out_label, float* count, int32_t b, int32_t C1, int32_t h, int32_t w, int32_t H,
                                      int32_t W, dupl_stream_t s) {
-    if (!logits || !other_label || !out_label || !count || b <= 0 || C1 <= 0 || h <= 0 || w <= 0) return DUPL_ERR_ARG;
+    if (!logits || !other_label || !out_label || !count || b <= 0 || C1 <= 0 || h <= 0 || w <= 0 || H < h || W < w)
+        return DUPL_ERR_ARG;
     DUPL_LAUNCH(seg_pseudo_label_kernel, dim3((H * W + 255) / 256, b), dim3(256), 0, (hipStream_t)s, logits, other_label,
                        ignore_index, conf_thr, (long long*)out_label, count, C1, h, w, H, W);
     return dupl_launch_status();

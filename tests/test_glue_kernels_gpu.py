@@ -16,94 +16,16 @@ import torch
 import torch.nn.functional as F
 
 import glue_ref as G
+from kernel_guard import (NAN, EPS24, PAD, SENT, _ALIVE, Guard, bits, nan_in, ratio_report, rnd, rndint, same_bits,  # noqa: F401
+                          stream)
 
 pytestmark = pytest.mark.gpu
-
-NAN = float("nan")
-EPS24 = 2.0 ** -24
-PAD = 64                     # floats of slack on either side: keeps the 256-byte alignment of the allocation
-SENT = {torch.float32: (torch.int32, 0x7FC5A5A5), torch.int32: (torch.int32, -0x5A5A5A5B),
-        torch.int64: (torch.int64, -0x5A5A5A5A5A5A5A5B)}
-
-
-def rnd(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g, dtype=torch.float32) * scale
-
-
-def rndint(lo, hi, *shape, seed=0):
-    return torch.randint(lo, hi, shape, generator=torch.Generator().manual_seed(seed))
-
-
-class Guard:
-    """A tensor of `shape` inside a larger device allocation; the slack holds a sentinel (a NaN payload for floats)."""
-
-    def __init__(self, shape, dev, dtype=torch.float32, init=None, front=PAD, back=PAD):
-        self.n = int(np.prod(shape)) if len(shape) else 1
-        self.front, self.back = front, back
-        self.buf = torch.empty(self.n + front + back, dtype=dtype, device=dev)
-        self.itype, self.pat = SENT[dtype]
-        self.buf.view(self.itype).fill_(self.pat)
-        self.view = self.buf[front:front + self.n].view(shape)
-        if init is not None:
-            self.view.copy_(init)
-
-    @property
-    def ptr(self):
-        return self.view.data_ptr()
-
-    def intact(self):
-        i = self.buf.view(self.itype).cpu()
-        return bool((i[:self.front] == self.pat).all()) and bool((i[self.front + self.n:] == self.pat).all())
-
-    def untouched(self):
-        return bool((self.buf.view(self.itype).cpu() == self.pat).all())
-
-    def cpu(self):
-        torch.cuda.synchronize()
-        assert self.intact(), "the kernel wrote outside its output"
-        return self.view.cpu()
-
-
-_ALIVE = []                  # inputs handed to a kernel as bare pointers stay allocated until the test is over
 
 
 @pytest.fixture(autouse=True)
 def _release_inputs():
     yield
     _ALIVE.clear()
-
-
-def nan_in(t, dev, front=PAD, back=PAD):
-    """t on the device inside a buffer whose slack is NaN; returns the view."""
-    t = t.contiguous()
-    buf = torch.full((t.numel() + front + back,), NAN, dtype=torch.float32, device=dev)
-    view = buf[front:front + t.numel()].view(t.shape)
-    view.copy_(t)
-    _ALIVE.append(buf)
-    return view
-
-
-def bits(t):
-    return t.contiguous().view(torch.int32 if t.element_size() == 4 else torch.int64)
-
-
-def same_bits(a, b):
-    return a.shape == b.shape and bool((bits(a) == bits(b)).all())
-
-
-def stream():
-    from dupl_amd import ops
-    return ops._stream()
-
-
-def ratio_report(tag, err, bound):
-    """worst err / bound, printed and returned; a zero bound admits only a zero error"""
-    err, bound = err.double(), bound.double().expand_as(err)
-    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, math.inf), torch.zeros_like(err)))
-    worst = float(r.max()) if r.numel() else 0.0
-    print(f"{tag}: worst err / bound {worst:.3f}")
-    return worst
 
 
 # =========================================================================================== tokens: global max pool

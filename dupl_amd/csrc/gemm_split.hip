@@ -126,43 +126,28 @@ __device__ __forceinline__ void gemm16_epilogue(const dupl_gemm16_desc& p, f32x1
 }
 
 
-// Epilogue through LDS (ring kernel): the wave parks its (alpha-scaled, main + cross / 2048) tile in its own LDS region
-// [32 WM][32 WN] floats and walks it back row-wise, one float4 (4 consecutive columns) per lane -- 64 lanes = 4 rows x 256
-// contiguous bytes at 32 WN = 64 -- so that every global access of the epilogue (C, planes, aux, res) is a full-width
-// vector access on whole 128-byte lines instead of 2 x 128-byte dword rows (fp32) / 2 x 64 bytes (planes) per
-// instruction, and the epilogue is a short runtime loop instead of 16 WM WN unrolled element bodies.
-// LDS banking: the b32 writes of one MFMA register cover 32 consecutive floats per half-wave; the b128 reads of a 16-lane
-// group cover two row segments that tile all 64 banks (unpadded rows of 32 / 64 floats) -- both conflict-free.
+// Epilogue through LDS (ring kernels): the wave parks its (alpha-scaled) tile in its own LDS region [TH][TW] floats and walks it back
+// row-wise, one float4 (4 consecutive columns) per lane -- 64 lanes = 4 rows x 256 contiguous bytes at TW = 64 -- so that every
+// global access of the epilogue (C, planes, aux, res) is a full-width vector access on whole 128-byte lines instead of 2 x 128-byte
+// dword rows (fp32) / 2 x 64 bytes (planes) per instruction, and the epilogue is a short runtime loop instead of unrolled element bodies.
+// This is the row walk, shared by both MFMA shapes: park(ps) writes pass ps of the wave's tile into `tile` (the NPS passes reuse the
+// region, same wave, in order), the walk reads it back.  ROT (the 16x16 MFMA's 4-register blocks): the floats of row r sit rotated by 16
+// columns when r & 4, see gemm16_epilogue_lds16.
 // Vector path needs N, ldc, ldo, ldr, ldaux multiples of 4 and 16-byte (8 for planes) aligned bases: `vec`, block-uniform;
 // otherwise, and in edge columns, the same values go out element-wise.
-// WMP: MFMA row tiles per pass (the region holds 32 WMP rows; the WM / WMP passes reuse it, same wave, in order).  SINGLE: the
-// cross terms were accumulated into accM (unscaled lo planes), accX is unused.
-template <int WM, int WN, int WMP, bool SINGLE>
-__device__ __forceinline__ void gemm16_epilogue_lds(const dupl_gemm16_desc& p, f32x16 (&accM)[WM][WN], f32x16 (&accX)[SINGLE ? 1 : WM][SINGLE ? 1 : WN],
-                                                    float* __restrict__ tile, const int mw0, const int nw, const int lane,
-                                                    const int ksplit, float& amx) {
-    constexpr int TW = 32 * WN, TH = 32 * WMP, LPR = TW / 4, RPI = 64 / LPR;
-    static_assert(WM % WMP == 0, "passes");
-    const int l31 = lane & 31, hf = lane >> 5;
+template <int TW, int TH, int NPS, bool ROT, class Park>
+__device__ __forceinline__ void gemm16_epilogue_rows(const dupl_gemm16_desc& p, Park&& park, float* __restrict__ tile, const int mw0,
+                                                     const int nw, const int lane, const int ksplit, float& amx) {
+    constexpr int LPR = TW / 4, RPI = 64 / LPR;
+    auto at = [](const int r, const int c) { return r * TW + (ROT ? ((c + ((r >> 2) & 1) * 16) & (TW - 1)) : c); };
     const int fl = p.flags;
     const bool f_pre = fl & DUPL_GEMM_STORE_PRE, f_gelu = fl & DUPL_GEMM_GELU, f_relu = fl & DUPL_GEMM_RELU;
     const bool f_acc = fl & DUPL_GEMM_ACCUM, f_dgelu = fl & DUPL_GEMM_MUL_DGELU, f_rmask = fl & DUPL_GEMM_MUL_RELUMASK;
-    const float alpha = (p.alpha_dev ? *p.alpha_dev : 1.f) * (p.post_scale != 0.f ? p.post_scale : 1.f);
     const float out_scale = p.out_exp > 0 ? ldexpf(1.f, p.out_exp) : 0.f;      // > 0: the planes go out in format 1
 #pragma unroll
-    for (int ps = 0; ps < WM / WMP; ++ps) {
+    for (int ps = 0; ps < NPS; ++ps) {
     const int mw = mw0 + ps * TH;
-#pragma unroll
-    for (int i = 0; i < WMP; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                float v;
-                if constexpr (SINGLE) v = accM[ps * WMP + i][j][e] * alpha;
-                else v = (accM[ps * WMP + i][j][e] + accX[ps * WMP + i][j][e] * LO_INV) * alpha;
-                tile[(i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hf) * TW + j * 32 + l31] = v;
-            }
+    park(ps);
     __half* Ch = static_cast<__half*>(p.C_hi);
     __half* Cl = static_cast<__half*>(p.C_lo);
     auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
@@ -178,7 +163,7 @@ __device__ __forceinline__ void gemm16_epilogue_lds(const dupl_gemm16_desc& p, f
             const int row = mw + r;
             if (row >= p.M) break;
             float* cp = p.C + (size_t)row * p.ldc + nw + ca;
-            const float v = tile[r * TW + ca];
+            const float v = tile[at(r, ca)];
             if (ksplit > 1) unsafeAtomicAdd(cp, v);
             else *cp += v;
         }
@@ -219,7 +204,7 @@ __device__ __forceinline__ void gemm16_epilogue_lds(const dupl_gemm16_desc& p, f
         if (r >= TH) break;
         const int row = mw + r;
         if (row >= p.M) break;
-        const f32x4 t = *reinterpret_cast<const f32x4*>(tile + r * TW + cl);
+        const f32x4 t = *reinterpret_cast<const f32x4*>(tile + at(r, cl));
         if (G16_ABL & 4) {
             if (t[0] + t[1] + t[2] + t[3] == 123.456f) p.C[0] = 1.f;
             continue;
@@ -295,6 +280,58 @@ _Pragma("unroll") for (int c = 0; c < 4; ++c)
         }   // rows of the chunk
     }
     }   // passes
+}
+
+// The row walk for accumulators of the 32x32 MFMA: the tile is main + cross / 2048, [32 WMP][32 WN] floats per pass.
+// LDS banking: the b32 writes of one MFMA register cover 32 consecutive floats per half-wave; the b128 reads of a 16-lane
+// group cover two row segments that tile all 64 banks (unpadded rows of 32 / 64 floats) -- both conflict-free.
+// WMP: MFMA row tiles per pass (the region holds 32 WMP rows; WM / WMP passes).  SINGLE: the cross terms were accumulated into
+// accM (unscaled lo planes), accX is unused.
+template <int WM, int WN, int WMP, bool SINGLE>
+__device__ __forceinline__ void gemm16_epilogue_lds(const dupl_gemm16_desc& p, f32x16 (&accM)[WM][WN], f32x16 (&accX)[SINGLE ? 1 : WM][SINGLE ? 1 : WN],
+                                                    float* __restrict__ tile, const int mw0, const int nw, const int lane,
+                                                    const int ksplit, float& amx) {
+    constexpr int TW = 32 * WN, TH = 32 * WMP;
+    static_assert(WM % WMP == 0, "passes");
+    const int l31 = lane & 31, hf = lane >> 5;
+    const float alpha = (p.alpha_dev ? *p.alpha_dev : 1.f) * (p.post_scale != 0.f ? p.post_scale : 1.f);
+    auto park = [&](const int ps) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < WMP; ++i)
+#pragma unroll
+            for (int j = 0; j < WN; ++j)
+#pragma unroll
+                for (int e = 0; e < 16; ++e) {
+                    float v;
+                    if constexpr (SINGLE) v = accM[ps * WMP + i][j][e] * alpha;
+                    else v = (accM[ps * WMP + i][j][e] + accX[ps * WMP + i][j][e] * LO_INV) * alpha;
+                    tile[(i * 32 + (e & 3) + 8 * (e >> 2) + 4 * hf) * TW + j * 32 + l31] = v;
+                }
+    };
+    gemm16_epilogue_rows<TW, TH, WM / WMP, false>(p, park, tile, mw0, nw, lane, ksplit, amx);
+}
+
+// The same for accumulators of the 16x16x32 MFMA (format 1, one set): RB x CB blocks of 4 registers, col = lane & 15, row =
+// 4 (lane >> 4) + reg; RBP row blocks per pass.  The b32 writes of one register put lanes l and l + 16 four rows apart, which is a
+// multiple of 32 banks at 64-float rows: rows with bit 2 set are stored rotated by 16 floats, so that a half-wave covers 32 banks;
+// the four rows of one b128 read instruction share that bit, their banks are permuted as a whole -- both stay conflict-free.
+template <int RB, int CB, int RBP>
+__device__ __forceinline__ void gemm16_epilogue_lds16(const dupl_gemm16_desc& p, f32x4 (&acc)[RB][CB], float* __restrict__ tile,
+                                                      const int mw0, const int nw, const int lane, const int ksplit, float& amx) {
+    constexpr int TW = 16 * CB, TH = 16 * RBP;
+    static_assert(RB % RBP == 0 && TW == 64, "passes; the rotation is laid out for 64-float rows");
+    const int l15 = lane & 15, q = lane >> 4;
+    const float alpha = (p.alpha_dev ? *p.alpha_dev : 1.f) * (p.post_scale != 0.f ? p.post_scale : 1.f);
+    auto park = [&](const int ps) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < RBP; ++i)
+#pragma unroll
+            for (int j = 0; j < CB; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    tile[(i * 16 + 4 * q + e) * TW + ((j * 16 + l15 + (q & 1) * 16) & (TW - 1))] = acc[ps * RBP + i][j][e] * alpha;
+    };
+    gemm16_epilogue_rows<TW, TH, RB / RBP, true>(p, park, tile, mw0, nw, lane, ksplit, amx);
 }
 
 
@@ -611,6 +648,14 @@ __global__ __launch_bounds__(64 * NWM * NWN, MINB) void gemm_f16x3_kernel(const 
 // s_waitcnt immediate (gfx9 encoding): lgkmcnt(0), expcnt untouched, vmcnt(n)
 #define WAIT_LGKM0_VM(n) ((((n) & 15) | (((n) >> 4) << 14)) | (7 << 4))
 
+template <int N, int I = 0, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    if constexpr (I < N) {
+        f(std::integral_constant<int, I>{});
+        static_for<N, I + 1>(f);
+    }
+}
+
 // issue-order hints (hipcc keeps ds_read / MFMA / DMA clusters apart otherwise): NMF MFMAs spread over NR fragment reads
 // (phase A) or over NR reads + ND DMA pieces (phase B: reads and DMA alternate while both remain)
 template <int NMF, int NR, int R = 0>
@@ -885,6 +930,210 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring_kernel(co
 
 
 // ---------------------------------------------------------------------------------------------------------------------------
+// The single-accumulator (format 1) ring kernel on v_mfma_f32_16x16x32_f16.  Same block and wave tiles (WM x WN still count 32 x 32
+// units), LDS stages, DMA ring and tile order as gemm_f16x3_ring_kernel<.., SINGLE = true>; the same MFMA cycles (3 x 16 per 16 x 16
+// block and k-tile instead of 2 x 3 x 32 per 32 x 32 block), accumulator registers and fragment reads.  What it is for: under this
+// loop the chip holds its clock down, and the clock it holds depends on the MFMA shape.
+//   * lane l holds row (l & 15), k = 8 (l >> 4) .. + 7 of an operand block: a k-tile (32) is ONE MFMA k-step, and a fragment is one
+//     whole 1 KB DMA piece (16 rows x 64 bytes) read by one ds_read_b128.  Source-side swizzle: chunk j of row r sits at chunk
+//     j ^ ((4 - (r >> 2)) & 3) -- conflict-free in all four lane groups of that read (the 32 x 32 kernels' (r >> 2) & 3 is 2-way here).
+//   * per accumulator and k-tile: hi.hi, hi.lo, lo.hi, in k order -- the same code in both block tiles, so a row's result does not
+//     depend on the tile it rides in.  The sums differ from the 32 x 32 x 16 kernels' in the last bits (32 products per MFMA, not 16).
+//   * pipeline: the B fragments of a k-tile (2 CB) are held through the tile, the A fragments go in WM phases of two row blocks
+//     (32 rows: 4 fragments), double-buffered: 64 fragment registers.  A phase walks its column blocks in order, so that the last
+//     phase can refill the B fragments in place, block by block.  Phase i < WM - 1 reads A(i + 1) under the MFMAs of A(i); then ONE
+//     counted s_waitcnt vmcnt + raw s_barrier (tile t + 1 landed, every wave done reading tile t); the last phase reads A(0) and B of
+//     tile t + 1 and issues the DMA of tile t + STAGES into tile t's stage.
+template <int WM, int WN, int NWM, int NWN, int WPS, int STAGES>
+__global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(const dupl_gemm16_desc p, const int g_gm) {
+    constexpr int BM = 32 * WM * NWM, BN = 32 * WN * NWN, NW = NWM * NWN;
+    constexpr int PA = BM / 16, PB = BN / 16;
+    constexpr int NP = 2 * PA + 2 * PB;
+    constexpr int STAGE = NP * 1024;
+    constexpr int PPW = NP / NW;
+    constexpr int RB = 2 * WM, CB = 2 * WN;          // 16 x 16 blocks of the wave tile
+    constexpr int NPH = WM;                          // phases of a k-tile: two row blocks each
+    constexpr int NMF = 3 * 2 * CB;                  // MFMAs of a phase
+    static_assert(NP % NW == 0, "pieces must divide over the waves");
+    static_assert(STAGES * STAGE <= 160 * 1024, "LDS");
+    static_assert((STAGES - 1) * PPW <= 63, "vmcnt range");
+    static_assert(NPH % 2 == 0, "the A fragment sets alternate by phase");
+    __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / NWN, wn = wave % NWN;
+
+    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
+    const int nblk = nbm * nbn;
+    const int bid = blockIdx.x;
+    const int q8 = nblk >> 3, r8 = nblk & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    const int lid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+    const int gspan = g_gm * nbn;
+    const int gid = lid / gspan, gin = lid - gid * gspan;
+    const int gfirst = gid * g_gm;
+    const int gsz = min(nbm - gfirst, g_gm);
+    const int tm = gfirst + gin % gsz, tn = gin / gsz;
+    const int m0 = tm * BM, n0 = tn * BN;
+    const int nt = p.K / TBK;
+
+    // ---- DMA plan (as gemm_f16x3_ring_kernel, with this kernel's swizzle): piece g = wave + NW * i
+    const int prow = lane >> 2;
+    const int jsrc = (lane & 3) ^ ((4 - (prow >> 2)) & 3);
+    const char* gp[PPW];
+#pragma unroll
+    for (int i = 0; i < PPW; ++i) {
+        const int g = wave + NW * i;
+        const __half* plane;
+        int ld, r0, R, q;
+        if (g < PA) { plane = static_cast<const __half*>(p.A_hi); ld = p.lda; r0 = m0; R = p.M; q = g; }
+        else if (g < 2 * PA) { plane = static_cast<const __half*>(p.A_lo); ld = p.lda; r0 = m0; R = p.M; q = g - PA; }
+        else if (g < 2 * PA + PB) { plane = static_cast<const __half*>(p.B_hi); ld = p.ldb; r0 = n0; R = p.N; q = g - 2 * PA; }
+        else { plane = static_cast<const __half*>(p.B_lo); ld = p.ldb; r0 = n0; R = p.N; q = g - 2 * PA - PB; }
+        const int row = min(r0 + q * 16 + prow, R - 1);
+        gp[i] = reinterpret_cast<const char*>(plane + (size_t)row * ld) + jsrc * 16;
+    }
+    auto dma_item = [&](auto dc, char* dst) __attribute__((always_inline)) {
+        constexpr int I = decltype(dc)::value;
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp[I],
+                                         (__attribute__((address_space(3))) void*)(dst + I * (NW * 1024)), 16, 0, 0);
+        gp[I] += TBK * 2;
+    };
+    auto issue = [&](int buf) __attribute__((always_inline)) {   // next k-tile of this block -> stage buf
+        static_for<PPW>([&](auto i) __attribute__((always_inline)) { dma_item(i, smem + buf * STAGE + wave * 1024); });
+    };
+
+    // ---- fragment addresses (bytes inside a stage): plane base + row * 64 + ((lane >> 4) ^ swizzle(row)) * 16
+    const int l15 = lane & 15;
+    const int ch = ((lane >> 4) ^ ((4 - (l15 >> 2)) & 3)) * 16;
+    const int a_off = (wm * (32 * WM) + l15) * 64 + ch, b_off = 2 * PA * 1024 + (wn * (32 * WN) + l15) * 64 + ch;
+
+    f32x4 acc[RB][CB];
+#pragma unroll
+    for (int i = 0; i < RB; ++i)
+#pragma unroll
+        for (int j = 0; j < CB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // A: two sets of {hi rb 0, hi rb 1, lo rb 0, lo rb 1}, alternating by phase; B: {hi cb .., lo cb ..} of the k-tile
+    h8 fa0[4], fa1[4], fb[2 * CB];
+    auto read_a = [&](auto rc, const char* st, const int ph, h8(&fa)[4]) __attribute__((always_inline)) {
+        constexpr int R = decltype(rc)::value;
+        fa[R] = *reinterpret_cast<const h8*>(st + (R >> 1) * (PA * 1024) + a_off + (2 * ph + (R & 1)) * 1024);
+    };
+    auto read_b = [&](auto jc, const char* st) __attribute__((always_inline)) {
+        constexpr int J = decltype(jc)::value;
+        fb[J] = *reinterpret_cast<const h8*>(st + b_off + J * 1024);
+        fb[CB + J] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_off + J * 1024);
+    };
+    // column block J of a phase: hi.hi, hi.lo, lo.hi on each of its two accumulators
+    auto mfma6 = [&](auto phc, auto jc, const h8(&fa)[4]) __attribute__((always_inline)) {
+        constexpr int PH = decltype(phc)::value, J = decltype(jc)::value;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[k], fb[J], acc[2 * PH + k][J], 0, 0, 0);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[k], fb[CB + J], acc[2 * PH + k][J], 0, 0, 0);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[2 + k], fb[J], acc[2 * PH + k][J], 0, 0, 0);
+    };
+    constexpr int S_MFMA = 0x008, S_DSR = 0x100, S_VMEM = 0x010;
+    // issue-order hint for one column block (6 MFMAs) with NRD fragment reads under it: one read behind each of the first MFMAs
+    auto hint6 = [](auto nrd) __attribute__((always_inline)) {
+        constexpr int NRD = decltype(nrd)::value;
+        static_for<NRD>([](auto) __attribute__((always_inline)) {
+            __builtin_amdgcn_sched_group_barrier(S_MFMA, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(S_DSR, 1, 0);
+        });
+        __builtin_amdgcn_sched_group_barrier(S_MFMA, 6 - NRD, 0);
+    };
+    // phases 0 .. NPH - 2 of the tile in stage st: the first two column blocks of phase i run over the reads of A(i + 1); the very
+    // first one also over the tile's own last B pair (its registers are busy to the end of the previous tile's last phase)
+    auto inner_phases = [&](const char* st) __attribute__((always_inline)) {
+        static_for<NPH - 1>([&](auto ph) __attribute__((always_inline)) {
+            constexpr int PH = decltype(ph)::value;
+            static_for<CB>([&](auto j) __attribute__((always_inline)) {
+                constexpr int J = decltype(j)::value;
+                constexpr int NRD = (J < 2 ? 2 : 0) + (PH == 0 && J == 0 ? 2 : 0);
+                if constexpr (PH == 0 && J == 0) read_b(std::integral_constant<int, CB - 1>{}, st);
+                if constexpr (J < 2) {
+                    read_a(std::integral_constant<int, 2 * J>{}, st, PH + 1, PH & 1 ? fa0 : fa1);
+                    read_a(std::integral_constant<int, 2 * J + 1>{}, st, PH + 1, PH & 1 ? fa0 : fa1);
+                }
+                mfma6(ph, j, PH & 1 ? fa1 : fa0);
+                hint6(std::integral_constant<int, NRD>{});
+            });
+        });
+    };
+    // the last phase.  LOAD: the fragments of the next tile (stage nx) are read under it -- A(0) under column block 0, the B pair of
+    // column block j IN PLACE under block j + 1, once the MFMAs of block j are out (the last pair: inner_phases); DMA: the PPW pieces of
+    // tile t + STAGES go out between the blocks.  The loads stand in the source in the order the hints pin them (an LDS read and an
+    // LDS-DMA write are ordered for the compiler).
+    auto last_phase = [&](auto loadc, auto dmac, const char* nx, char* dst) __attribute__((always_inline)) {
+        constexpr bool LOAD = decltype(loadc)::value, DMA = decltype(dmac)::value;
+        constexpr auto ph = std::integral_constant<int, NPH - 1>{};
+        static_for<CB>([&](auto j) __attribute__((always_inline)) {
+            constexpr int J = decltype(j)::value;
+            constexpr int D0 = J * PPW / CB, D1 = (J + 1) * PPW / CB;      // this block's DMA pieces
+            if constexpr (LOAD) {
+                if constexpr (J == 0) static_for<4>([&](auto r) __attribute__((always_inline)) { read_a(r, nx, 0, fa0); });
+                else read_b(std::integral_constant<int, J - 1>{}, nx);
+            }
+            if constexpr (DMA) static_for<D1 - D0>([&](auto i) __attribute__((always_inline)) {
+                dma_item(std::integral_constant<int, D0 + decltype(i)::value>{}, dst);
+            });
+            mfma6(ph, j, fa1);
+            hint6(std::integral_constant<int, LOAD ? (J == 0 ? 4 : 2) : 0>{});
+            if constexpr (DMA && D1 > D0) __builtin_amdgcn_sched_group_barrier(S_VMEM, D1 - D0, 0);
+        });
+    };
+    // ---- pipeline.  Tile t lives in stage t % STAGES.  Iteration t: the inner phases; lgkmcnt(0), vmcnt((STAGES - 2) PPW): my
+    // pieces of tile t + 1 landed (later tiles may still fly); s_barrier: every wave is done reading tile t; the last phase.  Never
+    // vmcnt(0) below the pieces in flight and never __syncthreads() in the steady state; the last STAGES iterations run without DMA.
+#pragma unroll
+    for (int s = 0; s < STAGES; ++s)
+        if (s < nt) issue(s);
+    if (nt >= STAGES) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 1) * PPW) : "memory");
+    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    static_for<4>([&](auto r) __attribute__((always_inline)) { read_a(r, smem, 0, fa0); });
+    static_for<CB - 1>([&](auto j) __attribute__((always_inline)) { read_b(j, smem); });
+    int rb = 0;
+    int t = 0;
+    for (; t + STAGES < nt; ++t) {
+        const int nb = rb + 1 == STAGES ? 0 : rb + 1;
+        inner_phases(smem + rb * STAGE);
+        __builtin_amdgcn_sched_barrier(0);      // the MFMAs of the inner phases stay in front of the wait (they are no memory operations)
+        __builtin_amdgcn_s_waitcnt(WAIT_LGKM0_VM((STAGES - 2) * PPW));   // the builtin, so that hipcc knows the fragments have landed
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        last_phase(std::true_type{}, std::true_type{}, smem + nb * STAGE, smem + rb * STAGE + wave * 1024);
+        rb = nb;
+    }
+    for (; t + 1 < nt; ++t) {
+        const int nb = rb + 1 == STAGES ? 0 : rb + 1;
+        inner_phases(smem + rb * STAGE);
+        __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_s_waitcnt(WAIT_LGKM0_VM(0));
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        last_phase(std::true_type{}, std::false_type{}, smem + nb * STAGE, nullptr);
+        rb = nb;
+    }
+    inner_phases(smem + rb * STAGE);
+    last_phase(std::false_type{}, std::false_type{}, nullptr, nullptr);
+
+    // every wave is done reading the stages and no DMA is in flight -> reuse the LDS for the epilogue tiles
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    constexpr int RBP = (NW * (16 * RB) * (16 * CB) * 4 <= STAGES * STAGE) ? RB : RB / 2;   // row blocks per epilogue pass
+    static_assert(NW * (16 * RBP) * (16 * CB) * 4 <= STAGES * STAGE, "epilogue tiles must fit the stages");
+    float amx = 0.f;
+    gemm16_epilogue_lds16<RB, CB, RBP>(p, acc, reinterpret_cast<float*>(smem) + wave * ((16 * RBP) * (16 * CB)), m0 + wm * (32 * WM),
+                                       n0 + wn * (32 * WN), lane, 1, amx);
+}
+
+
+// ---------------------------------------------------------------------------------------------------------------------------
 // Persistent form of the ring kernel (round 3): one block per CU walks over the output tiles (tile = blockIdx.x + k gridDim.x,
 // gridDim.x a multiple of 8 so that a block keeps its XCD and the XCD-aware tile order holds).  What it buys over one block per
 // tile: the three-stage prologue DMA of the NEXT tile is issued before the epilogue of the current one (the stages are free
@@ -1146,14 +1395,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(c
 // block that owns the tile (deterministic mode); ACC 0: the full epilogue (bias / activation / aux / planes / amax).
 typedef short s4v __attribute__((ext_vector_type(4)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
-
 // phase B of the k-major kernel: NR read instructions and ND DMA pieces alternate, the rarer kind spread over the other
 constexpr bool slot_is_read(int S, int NR, int ND) {
     int rd = 0, dd = 0;
@@ -1616,6 +1857,26 @@ extern "C" int dupl_gemm_f16x3_group(const dupl_gemm16_desc* descs, int32_t n, d
     return dupl_launch_status();
 }
 
+// Rows [0, M1) and [M1, M) of a forward launch as two descriptors (rows are independent: each on its own row range of every
+// operand).  False when the second part would have nothing to write.
+static bool g16_split_rows(const dupl_gemm16_desc& d, const int M1, dupl_gemm16_desc& d1, dupl_gemm16_desc& d2) {
+    d1 = d; d2 = d;
+    d1.M = M1;
+    d2.M = d.M - M1;
+    auto adv = [&](const void* q, size_t elems, size_t bytes) { return q ? static_cast<const void*>(static_cast<const char*>(q) + elems * bytes) : nullptr; };
+    d2.A_hi = adv(d.A_hi, (size_t)M1 * d.lda, 2); d2.A_lo = adv(d.A_lo, (size_t)M1 * d.lda, 2);
+    d2.C = (float*)adv(d.C, (size_t)M1 * d.ldc, 4);
+    d2.C_hi = (void*)adv(d.C_hi, (size_t)M1 * d.ldo, 2); d2.C_lo = (void*)adv(d.C_lo, (size_t)M1 * d.ldo, 2);
+    d2.res = (const float*)adv(d.res, (size_t)M1 * d.ldr, 4);
+    d2.aux = (float*)adv(d.aux, (size_t)M1 * d.ldaux, 4);
+    if (d.c_rows > 0) {             // fp32 outputs for the first c_rows rows only
+        if (d.c_rows <= M1) {       // ... all of them in part 1: part 2 writes planes only
+            d2.c_rows = 0; d2.C = nullptr; d2.aux = nullptr; d2.flags &= ~DUPL_GEMM_STORE_PRE;
+        } else { d1.c_rows = 0; d2.c_rows = d.c_rows - M1; }
+    }
+    return d2.C || d2.C_hi;
+}
+
 extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) {
     if (!d || d->struct_size != sizeof(dupl_gemm16_desc)) return DUPL_ERR_ARG;      // a caller built against another header
     if (!d->A_hi || !d->A_lo || !d->B_hi || !d->B_lo || d->M <= 0 || d->N <= 0 || d->K <= 0) return DUPL_ERR_ARG;
@@ -1625,7 +1886,7 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         return DUPL_ERR_ARG;
     {
         const int t = d->tile;
-        if (t != 0 && t != 3 && t != 5 && t != 6 && t != 7 && t != 8 && t != 10 && t != 11 && t != 12 && t != 14) return DUPL_ERR_ARG;
+        if (t != 0 && t != 3 && t != 5 && t != 6 && t != 7 && t != 8 && t != 10 && t != 11 && t != 12 && t != 14 && t != 18 && t != 22) return DUPL_ERR_ARG;
     }
     const int g16_tile = d->tile, g16_concurrency = d->concurrency > 0 ? d->concurrency : 1;
     const int g16_persist_blocks = d->persist_blocks ? d->persist_blocks : (g16_concurrency >= 2 ? 192 : 256);
@@ -1742,44 +2003,32 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         // 15 696 x 768 x 3 072 bias + residual: 295 vs 328; profiles/r06_tile16.txt): with one wave per SIMD nothing covers a wave's
         // own waits, the result tile 7 gave in round 3)
         const int nb22 = ((d->M + 255) / 256) * ((d->N + 255) / 256), nb21 = ((d->M + 255) / 256) * ((d->N + 127) / 128);
-        int t = (g16_tile == 8 || g16_tile == 12 || g16_tile == 14) ? g16_tile : (nb22 >= g16_f1_big_from ? 8 : 12);
+        // (18 / 22: the same two tiles on the 16x16x32 MFMA, gemm_f16x3_ring16_kernel; the launcher's own choice, since the clock the
+        // chip holds under this loop is higher on that shape.  Both tiles switch together: they are bit-identical to each other)
+        int t = (g16_tile == 8 || g16_tile == 12 || g16_tile == 14 || g16_tile == 18 || g16_tile == 22) ? g16_tile
+                                                                                                         : (nb22 >= g16_f1_big_from ? 18 : 22);
         if (d->K / TBK < 3 && t == 14) t = 12;
-        if (t == 8) {
+        if (t == 18) {
             // One block per CU and launch: nb22 tiles take ceil(nb22 / 256) rounds, and a last round that holds a few tiles costs as
             // much as a full one.  The merged ms-CAM / training pass of a step is exactly that case -- 21 976 rows = 86 row tiles, x
             // {12, 9, 3} column tiles = 1 032 / 774 / 258 tiles = 4, 3, 1 full rounds + 8 / 6 / 2 tiles (rocprofv3, one stream: 340 us
             // per launch where 6 280 + 15 696 rows took 290).  So: when the last round would be less than 30 % full, the rows of
             // the full rounds go to this kernel and the remaining row tiles to the 256 x 128 kernel (rows are independent: two
             // launches on the stream, each on its own row range of every operand).  Next to a second stream the tail is filled by
-            // the other student's blocks anyway; alone this is worth 9-22 % per launch.
+            // the other student's blocks anyway; alone this is worth 9-22 % per launch.  The automatic choice only.
             const int cn = (d->N + 255) / 256, rm = (d->M + 255) / 256, cus = 256;
             const int full = nb22 / cus, tail = nb22 - full * cus;
             const int r_big = full > 0 ? (full * cus) / cn : 0;
-            if (g16_tile == 0 && full > 0 && tail > 0 && tail * 10 < cus * 3 && r_big > 0 && r_big < rm && !d->amax_out) {
-                const int M1 = r_big * 256;
-                dupl_gemm16_desc d1 = *d, d2 = *d;
-                d1.M = M1;
-                d2.M = d->M - M1;
-                auto adv = [&](const void* q, size_t elems, size_t bytes) { return q ? static_cast<const void*>(static_cast<const char*>(q) + elems * bytes) : nullptr; };
-                d2.A_hi = adv(d->A_hi, (size_t)M1 * d->lda, 2); d2.A_lo = adv(d->A_lo, (size_t)M1 * d->lda, 2);
-                d2.C = (float*)adv(d->C, (size_t)M1 * d->ldc, 4);
-                d2.C_hi = (void*)adv(d->C_hi, (size_t)M1 * d->ldo, 2); d2.C_lo = (void*)adv(d->C_lo, (size_t)M1 * d->ldo, 2);
-                d2.res = (const float*)adv(d->res, (size_t)M1 * d->ldr, 4);
-                d2.aux = (float*)adv(d->aux, (size_t)M1 * d->ldaux, 4);
-                if (d->c_rows > 0) {             // fp32 outputs for the first c_rows rows only
-                    if (d->c_rows <= M1) {       // ... all of them in part 1: part 2 writes planes only
-                        d2.c_rows = 0; d2.C = nullptr; d2.aux = nullptr; d2.flags &= ~DUPL_GEMM_STORE_PRE;
-                    } else { d1.c_rows = 0; d2.c_rows = d->c_rows - M1; }
-                }
-                if (d2.C || d2.C_hi) {
-                    DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 4, 2, 2, true>), dim3((unsigned)(r_big * cn)), dim3(512), 0, s, d1, g16_group_ring);
-                    DUPL_LAUNCH((gemm_f16x3_ring_kernel<2, 2, 4, 2, 2, 3, true>),
-                                       dim3((unsigned)(((d2.M + 255) / 256) * ((d2.N + 127) / 128))), dim3(512), 0, s, d2, g16_group_ring);
-                    return dupl_launch_status();
-                }
-            }
-            DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 4, 2, 2, true>), blocks(256, 256), dim3(512), 0, s, *d, g16_group_ring);
+            dupl_gemm16_desc d1, d2;
+            if (g16_tile == 0 && full > 0 && tail > 0 && tail * 10 < cus * 3 && r_big > 0 && r_big < rm && !d->amax_out &&
+                g16_split_rows(*d, r_big * 256, d1, d2)) {
+                DUPL_LAUNCH((gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>), dim3((unsigned)(r_big * cn)), dim3(512), 0, s, d1, g16_group_ring);
+                DUPL_LAUNCH((gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>), dim3((unsigned)(((d2.M + 255) / 256) * ((d2.N + 127) / 128))),
+                            dim3(512), 0, s, d2, g16_group_ring);
+            } else DUPL_LAUNCH((gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>), blocks(256, 256), dim3(512), 0, s, *d, g16_group_ring);
         }
+        else if (t == 22) DUPL_LAUNCH((gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
+        else if (t == 8) DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 4, 2, 2, true>), blocks(256, 256), dim3(512), 0, s, *d, g16_group_ring);
         else if (t == 12) DUPL_LAUNCH((gemm_f16x3_ring_kernel<2, 2, 4, 2, 2, 3, true>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
         else
             DUPL_LAUNCH((gemm_f16x3_pring_kernel<2, 2, 4, 2, 2, false, true, 3>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
@@ -1803,7 +2052,7 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         DUPL_LAUNCH((gemm_f16x3_pring_kernel<2, 2, 4, 2, 2>), dim3((unsigned)grid), dim3(512), 0, s, *d, g16_group_ring);
         return dupl_launch_status();
     }
-    if (tile == 8 || tile == 9 || tile == 12 || tile == 14) tile = 5;      // single-accumulator tiles: format 1 operands only (above)
+    if (tile == 8 || tile == 9 || tile == 12 || tile == 14 || tile == 18 || tile == 22) tile = 5;      // single-accumulator tiles: format 1 operands only (above)
     if (tile == 6) DUPL_LAUNCH((gemm_f16x3_ring_kernel<2, 2, 4, 2, 2>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
     else if (tile == 7) DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 2, 1>), blocks(256, 128), dim3(256), 0, s, *d, g16_group_ring);
     else if (tile == 3) DUPL_LAUNCH((gemm_f16x3_kernel<2, 1, 2, 2, 2>), blocks(128, 64), dim3(256), 0, s, *d, g16_group_m);

@@ -81,7 +81,7 @@ int dupl_gemm_f32(const dupl_gemm_desc* d, dupl_stream_t stream);
 /* ---------------------------------------------------------------------------------------------
  * fp32-equivalent GEMM on the f16 matrix cores by operand splitting (csrc/gemm_split.hip):
  *   x = hi + lo/2048 with hi = fp16(x), lo = fp16((x - hi) * 2048);  a*b ~= hi_a hi_b + (hi_a lo_b + lo_a hi_b)/2048,
- * fp32 accumulation, 3 v_mfma_f32_32x32x16_f16 per 32x32x16 block.  Same reference sites as dupl_gemm_f32 for the
+ * fp32 accumulation, 3 v_mfma_f32_32x32x16_f16 per 32x32x16 block (format 1 forward: 3 v_mfma_f32_16x16x32_f16 per 16x16x32 block).  Same reference sites as dupl_gemm_f32 for the
  * k-contiguous x k-contiguous case (every nn.Linear forward: vit.py:92-102,115-122,136).  Operands are passed as two
  * fp16 planes each ([rows][ld] halfs); the result can be written as fp32 and / or as planes (the next GEMM's A operand).
  *   C = act(alpha * A . B^T + bias) (+ res);   flags: DUPL_GEMM_GELU | DUPL_GEMM_RELU | DUPL_GEMM_STORE_PRE (aux =
@@ -125,7 +125,9 @@ typedef struct dupl_gemm16_desc {
     int32_t tile;                         /* block tile.  Format 0 operands: 3: 128x64 on 4 waves, 5: 128x128 on 8 waves, 6 / 7: 256x128
                                              ring kernel on 8 / 4 waves, 10: its persistent form, 11: the stream-K form of that for
                                              DUPL_GEMM_ACCUM.  Format 1 (one accumulator set): 8: 256x256 on 8 waves, 12: 256x128, 14:
-                                             persistent 256x128 */
+                                             persistent 256x128 -- all on v_mfma_f32_32x32x16_f16; 18: 256x256 and 22: 256x128 on
+                                             v_mfma_f32_16x16x32_f16 (what 0 picks for k-contiguous operands; 18 and 22 are bit-identical
+                                             to each other, and differ from 8 / 12 in the last bits: 32 products per MFMA instead of 16) */
     int32_t concurrency;                  /* how many streams issue split GEMMs at the same time (2 while the two students of
                                              siamese_network run on their own streams, model_dupl.py:157-213): tile heuristic input */
     int32_t persist_blocks;               /* blocks of the persistent kernels, a multiple of 8 (0: 256 alone, 192 at concurrency 2) */

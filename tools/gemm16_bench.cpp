@@ -5,9 +5,13 @@
 // effective shader clock of the timed region (s_memtime ticks of a spinning probe are not needed: wall_clock64 vs clock64).
 //
 // build:  hipcc -O2 --offload-arch=gfx950 -Iinclude tools/gemm16_bench.cpp -Ldupl_amd -ldupl_hip -Wl,-rpath,'$ORIGIN/../dupl_amd' -o tools/gemm16_bench
-// usage:  tools/gemm16_bench [-t 5,6,7] [-n iters] [-s fwd|bwd|all|MxNxK[,MxNxK...]] [-e epilogue] [-c] [-2]
+// usage:  tools/gemm16_bench [-t 5,6,7] [-n iters] [-s fwd|bwd|all|MxNxK[,MxNxK...]] [-e epilogue] [-c] [-2] [-r rounds]
 //         -e: 0 fp32 out (default), 1 planes out, 2 bias+gelu+store_pre -> planes, 3 bias+res fp32, 4 accumulate (split-K)
 //         -c: correctness only      -2: run every launch on two streams concurrently (the step's two students)
+//         -r: A/B mode -- the variants take turns, `rounds` times each (one process, one device); per variant the median and the minimum
+//             time per launch and the median shader clock of its timed regions (with -f: tiles 8 / 12 against 18 / 22)
+//         Without -r a variant prints `t<tile> <TF/s-eq> <GHz> (<err>)`: the shader clock of the timed region is a column of its own, which
+//         the profiles/* tables made with this tool before it was added do not have.
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <cstdio>
@@ -15,6 +19,7 @@
 #include <cstring>
 #include <string>
 #include <vector>
+#include <algorithm>
 #include <cmath>
 #include "dupl_hip.h"
 
@@ -117,7 +122,7 @@ int main(int argc, char** argv) {
     int iters = 20, epi = 0, probe_iters = 40000, window_ms = 0;
     bool check_only = false, two = false, dbg = false, probe = false, f1 = false;   // f1: format 1 operand planes (single accumulator)
     std::string sel = "fwd", layout = "nn";
-    int group = 0, sk_slices = 0;
+    int group = 0, sk_slices = 0, rounds = 0;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "-t") && i + 1 < argc) tiles = parse_ints(argv[++i]);
         else if (!strcmp(argv[i], "-n") && i + 1 < argc) iters = atoi(argv[++i]);
@@ -128,10 +133,11 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "-2")) two = true;
         else if (!strcmp(argv[i], "-K") && i + 1 < argc) sk_slices = atoi(argv[++i]);   // stream-K forms: 0 heuristic, n slices, -1 equal runs
         else if (!strcmp(argv[i], "-g") && i + 1 < argc) group = atoi(argv[++i]);
+        else if (!strcmp(argv[i], "-r") && i + 1 < argc) rounds = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-L") && i + 1 < argc) layout = argv[++i];   // nn (default) | nk: B k-major (dgrad) | kk: A and B k-major (wgrad, use -e 4)
         else if (!strcmp(argv[i], "-p")) probe = true;
         else if (!strcmp(argv[i], "-P") && i + 1 < argc) { probe = true; probe_iters = atoi(argv[++i]); }
-        else if (!strcmp(argv[i], "-f")) f1 = true;     // format 1 planes: A * 2^3, B * 2^9, unscaled lo; tiles 8 (256 x 256) / 12 (256 x 128)
+        else if (!strcmp(argv[i], "-f")) f1 = true;     // format 1 planes: A * 2^3, B * 2^9, unscaled lo; tiles 8 / 18 (256 x 256), 12 / 22 (256 x 128)
         else if (!strcmp(argv[i], "-d")) dbg = true;   // ablation build with G16_ABL & 16: per-block s_memtime stamps through aux
     }
     const int akm = layout.size() > 0 && layout[0] == 'k', bkm = layout.size() > 1 && layout[1] == 'k';
@@ -258,7 +264,11 @@ int main(int argc, char** argv) {
             CK(hipDeviceSynchronize());
         }
         printf("%5dx%4dx%4d:", M, N, K);
-        for (int tile : tiles) {
+        std::vector<std::vector<double>> r_us(tiles.size()), r_ghz(tiles.size());
+        std::vector<float> r_err(tiles.size(), -1.f);
+        for (int round = 0; round < (rounds > 0 ? rounds : 1); ++round)
+        for (size_t ti = 0; ti < tiles.size(); ++ti) {
+            const int tile = tiles[ti];
             dupl_gemm16_desc d0 = desc(0);
             d0.tile = tile;
             if (epi == 4) CK(hipMemsetAsync(C[0], 0, nC * 4, st[0]));
@@ -350,9 +360,23 @@ int main(int argc, char** argv) {
                 if (nb) printf(" {%.2f GHz in-block, span %.0f us}", clk / nb, (double)(w1 - w0) / 100.0);
                 if (nb) printf(" [blocks %ld: prologue %.0f, loop %.0f, epilogue %.0f cyc]", nb, pro / nb, loop / nb, epil / nb);
             }
-            (void)ghz;
-            printf("  t%d %5.0f (%.1e)", tile, tf, rel);
+            if (rounds > 0) {
+                r_us[ti].push_back(ms * 1e3 / iters);
+                r_ghz[ti].push_back(ghz);
+                r_err[ti] = rel;
+                continue;
+            }
+            printf("  t%d %5.0f %.2f GHz (%.1e)", tile, tf, ghz, rel);
         }
+        if (rounds > 0)
+            for (size_t ti = 0; ti < tiles.size(); ++ti) {
+                if (r_us[ti].empty()) continue;
+                std::sort(r_us[ti].begin(), r_us[ti].end());
+                std::sort(r_ghz[ti].begin(), r_ghz[ti].end());
+                const size_t n = r_us[ti].size();
+                printf("  t%d med %.1f min %.1f max %.1f us %.2f GHz (%.1e)", tiles[ti], r_us[ti][n / 2], r_us[ti][0], r_us[ti][n - 1],
+                       r_ghz[ti][n / 2], r_err[ti]);
+            }
         printf("\n");
         fflush(stdout);
         for (int s = 0; s < ns; ++s) {

@@ -514,22 +514,124 @@ __device__ __forceinline__ void gemm16_epilogue_side(const dupl_gemm16_desc& p, 
         }
 }
 
+// ---- shared by the kernels below: the block tile's geometry, the block -> tile order, the piece DMA and the 32x32x16 fragment set
 // WM x WN: 32x32 MFMA tiles per wave; NWM x NWN: waves per block.  Block tile (32 WM NWM) x (32 WN NWN) x 32.
+template <int WM, int WN, int NWM, int NWN>
+struct RingGeom {
+    static constexpr int BM = 32 * WM * NWM, BN = 32 * WN * NWN, NW = NWM * NWN;
+    static constexpr int PA = BM / 16, PB = BN / 16;          // 16-row x 64-byte DMA pieces per operand plane and k-tile
+    static constexpr int NP = 2 * PA + 2 * PB;                // pieces per k-tile; LDS image: piece g at g * 1024 bytes
+    static constexpr int STAGE = NP * 1024;
+    static constexpr int PPW = NP / NW;                       // pieces per wave
+    static constexpr int NMF = 3 * WM * WN, NR = 2 * (WM + WN);   // MFMAs / fragment reads of a k-step (32x32x16)
+    static_assert(NP % NW == 0, "pieces must divide over the waves");
+};
+
+// Block -> tile: XCD-aware bijective remap + grouped row-tile order (same scheme as gemm.hip).  Blocks are dealt to the 8 XCDs
+// round-robin; XCD x takes the x-th run of q8 (+ 1 for x < r8) positions of the tile list `lid`, and the list walks groups of g_gm row
+// tiles, all column tiles of a group, row tile fastest.
+template <int BM, int BN>
+struct TileOrder {
+    int nbm, g_gm, nblk, q8, r8, gspan;
+    __device__ __forceinline__ TileOrder(const int nbm_, const int nbn, const int g_gm_)
+        : nbm(nbm_), g_gm(g_gm_), nblk(nbm_ * nbn), q8(nblk >> 3), r8(nblk & 7), gspan(g_gm_ * nbn) {}
+    __device__ __forceinline__ void lid_origin(const int lid, int& m0, int& n0) const {
+        const int gid = lid / gspan, gin = lid - gid * gspan;
+        const int gfirst = gid * g_gm;
+        const int gsz = min(nbm - gfirst, g_gm);
+        m0 = (gfirst + gin % gsz) * BM;
+        n0 = (gin / gsz) * BN;
+    }
+    __device__ __forceinline__ void tile_origin(const int bid, int& m0, int& n0) const {
+        const int xcd = bid & 7, idx = bid >> 3;
+        lid_origin((xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx, m0, n0);
+    }
+    // a block whose first index is past the last tile of its XCD's share has nothing to do (idx >= q8 + (xcd < r8))
+    __device__ __forceinline__ bool has_tile(const int bid) const { return (bid >> 3) < q8 + ((bid & 7) < r8 ? 1 : 0); }
+};
+
+// One 1 KB piece of a k-contiguous operand plane -> LDS by direct-to-LDS DMA; the source steps to the next k-tile.
+__device__ __forceinline__ void g16_dma_piece(const char*& gp, char* dst) {
+    if (!(G16_ABL & 1))
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp, (__attribute__((address_space(3))) void*)dst,
+                                         16, 0, 0);
+    gp += TBK * 2;
+}
+
+// The fragment set of the 32x32x16 MFMA, shared by the ring kernel and its persistent form.  A set is h8 fa[2 WM], fb[2 WN]: [0, W) hi
+// planes, [W, 2 W) lo planes.  a_row / b_row: this lane's row offsets inside a stage (bytes); cs: the 16-byte chunk of the k-step.
+template <int WM, int WN, int PA, int PB>
+struct Frag32 {
+    int a_row, b_row;
+    __device__ __forceinline__ void read_frags(const char* st, const int cs, h8 (&fa)[2 * WM], h8 (&fb)[2 * WN]) const {
+#pragma unroll
+        for (int i = 0; i < WM; ++i) {
+            fa[i] = *reinterpret_cast<const h8*>(st + a_row + i * 2048 + cs);
+            fa[WM + i] = *reinterpret_cast<const h8*>(st + PA * 1024 + a_row + i * 2048 + cs);
+        }
+#pragma unroll
+        for (int j = 0; j < WN; ++j) {
+            fb[j] = *reinterpret_cast<const h8*>(st + b_row + j * 2048 + cs);
+            fb[WN + j] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_row + j * 2048 + cs);
+        }
+    }
+    // the R-th of those reads alone.  Phase B: fragment reads of the next tile and DMA pieces alternate IN SOURCE ORDER (an LDS read
+    // and an LDS-DMA write are ordered for the compiler, so the issue-order hints can only follow the source)
+    template <int R>
+    __device__ __forceinline__ void read_item(const char* st, const int cs, h8 (&fa)[2 * WM], h8 (&fb)[2 * WN]) const {
+        if constexpr (R < WM) fa[R] = *reinterpret_cast<const h8*>(st + a_row + R * 2048 + cs);
+        else if constexpr (R < 2 * WM) fa[R] = *reinterpret_cast<const h8*>(st + PA * 1024 + a_row + (R - WM) * 2048 + cs);
+        else if constexpr (R < 2 * WM + WN) fb[R - 2 * WM] = *reinterpret_cast<const h8*>(st + b_row + (R - 2 * WM) * 2048 + cs);
+        else fb[R - 2 * WM] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_row + (R - 2 * WM - WN) * 2048 + cs);
+    }
+    // three passes (main, cross hi x lo, cross lo x hi), kept apart for the MFMA pipe: an accumulator is touched once per
+    // pass, WM WN MFMAs apart (sched_barrier: nothing but MFMAs is pinned, reads and DMA may cross).  SINGLE (format 1 operands):
+    // the cross terms go into accM, accX is unused.
+    template <bool SINGLE>
+    static __device__ __forceinline__ void mfmas(const h8 (&fa)[2 * WM], const h8 (&fb)[2 * WN], f32x16 (&accM)[WM][WN],
+                                                 f32x16 (&accX)[SINGLE ? 1 : WM][SINGLE ? 1 : WN]) {
+        constexpr int XMFMA = 0x7ff & ~0x8;
+        if (G16_ABL & 2) {
+#pragma unroll
+            for (int i = 0; i < 2 * WM; ++i) asm volatile("" ::"v"(fa[i]));
+#pragma unroll
+            for (int j = 0; j < 2 * WN; ++j) asm volatile("" ::"v"(fb[j]));
+            return;
+        }
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+            for (int j = 0; j < WN; ++j) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[j], accM[i][j], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(XMFMA);
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+            for (int j = 0; j < WN; ++j) {
+                if constexpr (SINGLE) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[WN + j], accM[i][j], 0, 0, 0);
+                else accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[WN + j], accX[i][j], 0, 0, 0);
+            }
+        __builtin_amdgcn_sched_barrier(XMFMA);
+#pragma unroll
+        for (int i = 0; i < WM; ++i)
+#pragma unroll
+            for (int j = 0; j < WN; ++j) {
+                if constexpr (SINGLE) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[WM + i], fb[j], accM[i][j], 0, 0, 0);
+                else accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[WM + i], fb[j], accX[i][j], 0, 0, 0);
+            }
+    }
+};
+
 template <int WM, int WN, int NWM, int NWN, int MINB>
 __global__ __launch_bounds__(64 * NWM * NWN, MINB) void gemm_f16x3_kernel(const dupl_gemm16_desc p, const int g_gm) {
-    constexpr int BM = 32 * WM * NWM, BN = 32 * WN * NWN, NW = NWM * NWN;
-    constexpr int PA = BM / 16, PB = BN / 16;          // 16-row x 64-byte DMA pieces per operand plane and k-tile
-    constexpr int NP = 2 * PA + 2 * PB;                // pieces per k-tile; LDS image: piece g at g * 1024 bytes
-    constexpr int STAGE = NP * 1024;
-    constexpr int PPW = NP / NW;                       // pieces per wave
-    static_assert(NP % NW == 0, "pieces must divide over the waves");
+    using G = RingGeom<WM, WN, NWM, NWN>;
+    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB, STAGE = G::STAGE, PPW = G::PPW;
     __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
     const int wm = wave / NWN, wn = wave % NWN;
     const int l31 = lane & 31, hf = lane >> 5;
 
-    // ---- tile id: XCD-aware bijective remap + grouped row-tile order (same scheme as gemm.hip)
+    // ---- tile id: TileOrder::tile_origin written out (through the struct one scalar add of this kernel comes out commuted)
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
     const int nblk = nbm * nbn;
     const int bid = blockIdx.x;
@@ -572,6 +674,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, MINB) void gemm_f16x3_kernel(const 
     const int sw = (l31 >> 2) & 3;
     const int a_row = (wm * (32 * WM) + l31) * 64, b_row = 2 * PA * 1024 + (wn * (32 * WN) + l31) * 64;
     const int c0 = ((0 | hf) ^ sw) * 16, c1 = ((2 | hf) ^ sw) * 16;
+    const Frag32<WM, WN, PA, PB> frag{a_row, b_row};
 
     f32x16 accM[WM][WN], accX[WM][WN];
 #pragma unroll
@@ -601,29 +704,18 @@ __global__ __launch_bounds__(64 * NWM * NWN, MINB) void gemm_f16x3_kernel(const 
         const char* st = smem + (t & 1) * STAGE;
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            const int cs = s == 0 ? c0 : c1;
-            h8 ah[WM], al[WM], bh[WN], bl[WN];
-#pragma unroll
-            for (int i = 0; i < WM; ++i) {
-                ah[i] = *reinterpret_cast<const h8*>(st + a_row + i * 2048 + cs);
-                al[i] = *reinterpret_cast<const h8*>(st + PA * 1024 + a_row + i * 2048 + cs);
-            }
-#pragma unroll
-            for (int j = 0; j < WN; ++j) {
-                bh[j] = *reinterpret_cast<const h8*>(st + b_row + j * 2048 + cs);
-                bl[j] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_row + j * 2048 + cs);
-            }
+            h8 fa[2 * WM], fb[2 * WN];
+            frag.read_frags(st, s == 0 ? c0 : c1, fa, fb);
 #pragma unroll
             for (int i = 0; i < WM; ++i)
 #pragma unroll
                 for (int j = 0; j < WN; ++j) {
-                    accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], accM[i][j], 0, 0, 0);
-                    accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl[j], accX[i][j], 0, 0, 0);
-                    accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh[j], accX[i][j], 0, 0, 0);
+                    accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[j], accM[i][j], 0, 0, 0);
+                    accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[WN + j], accX[i][j], 0, 0, 0);
+                    accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[WM + i], fb[j], accX[i][j], 0, 0, 0);
                 }
         }
     }
-
     float amx = 0.f;
     gemm16_epilogue<WM, WN>(p, accM, accX, m0 + wm * (32 * WM), n0 + wn * (32 * WN), m0 + BM <= p.M && n0 + BN <= p.N, l31, hf,
                             ksplit, amx);
@@ -702,13 +794,9 @@ __device__ __forceinline__ void loads_b(FR& read_item, FD& dma_item, const char*
 
 template <int WM, int WN, int NWM, int NWN, int WPS, int STAGES = 3, bool SINGLE = false>
 __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring_kernel(const dupl_gemm16_desc p, const int g_gm) {
-    constexpr int BM = 32 * WM * NWM, BN = 32 * WN * NWN, NW = NWM * NWN;
-    constexpr int PA = BM / 16, PB = BN / 16;
-    constexpr int NP = 2 * PA + 2 * PB;
-    constexpr int STAGE = NP * 1024;
-    constexpr int PPW = NP / NW;
-    constexpr int NMF = 3 * WM * WN, NR = 2 * (WM + WN);
-    static_assert(NP % NW == 0, "pieces must divide over the waves");
+    using G = RingGeom<WM, WN, NWM, NWN>;
+    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB, STAGE = G::STAGE, PPW = G::PPW;
+    constexpr int NMF = G::NMF, NR = G::NR;
     static_assert(STAGES * STAGE <= 160 * 1024, "LDS");
     static_assert((STAGES - 1) * PPW <= 63, "vmcnt range");
     __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE];
@@ -717,6 +805,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring_kernel(co
     const int wm = wave / NWN, wn = wave % NWN;
     const int l31 = lane & 31, hf = lane >> 5;
 
+    // tile id: TileOrder::tile_origin written out, as in gemm_f16x3_kernel
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
     const int nblk = nbm * nbn;
     const int bid = blockIdx.x;
@@ -763,10 +852,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring_kernel(co
         char* dst = smem + buf * STAGE + wave * 1024;
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
-            if (!(G16_ABL & 1))
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp[i],
-                                                 (__attribute__((address_space(3))) void*)(dst + i * (NW * 1024)), 16, 0, 0);
-            gp[i] += TBK * 2;
+            g16_dma_piece(gp[i], dst + i * (NW * 1024));
         }
     };
 
@@ -787,65 +873,15 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring_kernel(co
             }
     // two fragment sets: F0 = k-step 0 of a tile, F1 = k-step 1; [0, W) hi planes, [W, 2 W) lo planes
     h8 f0a[2 * WM], f0b[2 * WN], f1a[2 * WM], f1b[2 * WN];
-    auto read_frags = [&](const char* st, const int cs, h8(&fa)[2 * WM], h8(&fb)[2 * WN]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-            fa[i] = *reinterpret_cast<const h8*>(st + a_row + i * 2048 + cs);
-            fa[WM + i] = *reinterpret_cast<const h8*>(st + PA * 1024 + a_row + i * 2048 + cs);
-        }
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            fb[j] = *reinterpret_cast<const h8*>(st + b_row + j * 2048 + cs);
-            fb[WN + j] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_row + j * 2048 + cs);
-        }
-    };
-    // three passes (main, cross hi x lo, cross lo x hi), kept apart for the MFMA pipe: an accumulator is touched once per
-    // pass, WM WN MFMAs apart (sched_barrier: nothing but MFMAs is pinned, reads and DMA may cross)
-    constexpr int XMFMA = 0x7ff & ~0x8;
-    auto mfmas = [&](const h8(&fa)[2 * WM], const h8(&fb)[2 * WN]) __attribute__((always_inline)) {
-        if (G16_ABL & 2) {
-#pragma unroll
-            for (int i = 0; i < 2 * WM; ++i) asm volatile("" ::"v"(fa[i]));
-#pragma unroll
-            for (int j = 0; j < 2 * WN; ++j) asm volatile("" ::"v"(fb[j]));
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[j], accM[i][j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(XMFMA);
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j) {
-                if constexpr (SINGLE) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[WN + j], accM[i][j], 0, 0, 0);
-                else accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[WN + j], accX[i][j], 0, 0, 0);
-            }
-        __builtin_amdgcn_sched_barrier(XMFMA);
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j) {
-                if constexpr (SINGLE) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[WM + i], fb[j], accM[i][j], 0, 0, 0);
-                else accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[WM + i], fb[j], accX[i][j], 0, 0, 0);
-            }
-    };
-    // phase B: fragment reads of the next tile and DMA pieces alternate IN SOURCE ORDER (an LDS read and an LDS-DMA write
-    // are ordered for the compiler, so the issue-order hints can only follow the source)
+    const Frag32<WM, WN, PA, PB> frag{a_row, b_row};
+    auto read_frags = [&](const char* st, const int cs, h8(&fa)[2 * WM], h8(&fb)[2 * WN]) __attribute__((always_inline)) { frag.read_frags(st, cs, fa, fb); };
+    auto mfmas = [&](const h8(&fa)[2 * WM], const h8(&fb)[2 * WN]) __attribute__((always_inline)) { frag.template mfmas<SINGLE>(fa, fb, accM, accX); };
     auto read_item = [&](auto rc, const char* st, const int cs, h8(&fa)[2 * WM], h8(&fb)[2 * WN]) __attribute__((always_inline)) {
-        constexpr int R = decltype(rc)::value;
-        if constexpr (R < WM) fa[R] = *reinterpret_cast<const h8*>(st + a_row + R * 2048 + cs);
-        else if constexpr (R < 2 * WM) fa[R] = *reinterpret_cast<const h8*>(st + PA * 1024 + a_row + (R - WM) * 2048 + cs);
-        else if constexpr (R < 2 * WM + WN) fb[R - 2 * WM] = *reinterpret_cast<const h8*>(st + b_row + (R - 2 * WM) * 2048 + cs);
-        else fb[R - 2 * WM] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_row + (R - 2 * WM - WN) * 2048 + cs);
+        frag.template read_item<decltype(rc)::value>(st, cs, fa, fb);
     };
     auto dma_item = [&](auto dc, char* dst) __attribute__((always_inline)) {
         constexpr int I = decltype(dc)::value;
-        if (!(G16_ABL & 1))
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp[I],
-                                             (__attribute__((address_space(3))) void*)(dst + I * (NW * 1024)), 16, 0, 0);
-        gp[I] += TBK * 2;
+        g16_dma_piece(gp[I], dst + I * (NW * 1024));
     };
     // ---- pipeline.  Tile t lives in stage t % 3.  Iteration t:
     //   phase A:  read F1(t)                      | MFMAs on F0(t)
@@ -946,15 +982,11 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring_kernel(co
 //     tile t + 1 and issues the DMA of tile t + STAGES into tile t's stage.
 template <int WM, int WN, int NWM, int NWN, int WPS, int STAGES>
 __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(const dupl_gemm16_desc p, const int g_gm) {
-    constexpr int BM = 32 * WM * NWM, BN = 32 * WN * NWN, NW = NWM * NWN;
-    constexpr int PA = BM / 16, PB = BN / 16;
-    constexpr int NP = 2 * PA + 2 * PB;
-    constexpr int STAGE = NP * 1024;
-    constexpr int PPW = NP / NW;
+    using G = RingGeom<WM, WN, NWM, NWN>;
+    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB, STAGE = G::STAGE, PPW = G::PPW;
     constexpr int RB = 2 * WM, CB = 2 * WN;          // 16 x 16 blocks of the wave tile
     constexpr int NPH = WM;                          // phases of a k-tile: two row blocks each
     constexpr int NMF = 3 * 2 * CB;                  // MFMAs of a phase
-    static_assert(NP % NW == 0, "pieces must divide over the waves");
     static_assert(STAGES * STAGE <= 160 * 1024, "LDS");
     static_assert((STAGES - 1) * PPW <= 63, "vmcnt range");
     static_assert(NPH % 2 == 0, "the A fragment sets alternate by phase");
@@ -963,6 +995,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / NWN, wn = wave % NWN;
 
+    // tile id: TileOrder::tile_origin written out, as in gemm_f16x3_kernel
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
     const int nblk = nbm * nbn;
     const int bid = blockIdx.x;
@@ -995,9 +1028,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
     }
     auto dma_item = [&](auto dc, char* dst) __attribute__((always_inline)) {
         constexpr int I = decltype(dc)::value;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp[I],
-                                         (__attribute__((address_space(3))) void*)(dst + I * (NW * 1024)), 16, 0, 0);
-        gp[I] += TBK * 2;
+        g16_dma_piece(gp[I], dst + I * (NW * 1024));
     };
     auto issue = [&](int buf) __attribute__((always_inline)) {   // next k-tile of this block -> stage buf
         static_for<PPW>([&](auto i) __attribute__((always_inline)) { dma_item(i, smem + buf * STAGE + wave * 1024); });
@@ -1148,39 +1179,19 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
 // that every piece has the >= 3 k-steps the three-stage prologue needs.
 template <int WM, int WN, int NWM, int NWN, int WPS, bool SK = false, bool SINGLE = false, int STAGES = 3>
 __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(const dupl_gemm16_desc p, const int g_gm) {
-    constexpr int BM = 32 * WM * NWM, BN = 32 * WN * NWN, NW = NWM * NWN;
-    constexpr int PA = BM / 16, PB = BN / 16;
-    constexpr int NP = 2 * PA + 2 * PB;
-    constexpr int STAGE = NP * 1024;
-    constexpr int PPW = NP / NW;
-    constexpr int NMF = 3 * WM * WN, NR = 2 * (WM + WN);
+    using G = RingGeom<WM, WN, NWM, NWN>;
+    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB, STAGE = G::STAGE, PPW = G::PPW;
+    constexpr int NMF = G::NMF, NR = G::NR;
     constexpr int SIDE = NW * 2048;
-    static_assert(NP % NW == 0, "pieces must divide over the waves");
     static_assert(STAGES * STAGE + SIDE <= 160 * 1024, "LDS");
     __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE + SIDE];
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave / NWN, wn = wave % NWN;
     const int l31 = lane & 31, hf = lane >> 5;
-    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nblk = nbm * nbn;
+    const TileOrder<BM, BN> order((p.M + BM - 1) / BM, (p.N + BN - 1) / BN, g_gm);
     const int ntf = p.K / TBK;                    // k-steps of a whole tile, >= STAGES (host)
     int nt = ntf;                                 // k-steps of the current piece (SK: a part of the tile's)
-    const int q8 = nblk >> 3, r8 = nblk & 7;
-    const int gspan = g_gm * nbn;
-    auto lid_origin = [&](const int lid, int& m0, int& n0) __attribute__((always_inline)) {
-        const int gid = lid / gspan, gin = lid - gid * gspan;
-        const int gfirst = gid * g_gm;
-        const int gsz = min(nbm - gfirst, g_gm);
-        m0 = (gfirst + gin % gsz) * BM;
-        n0 = (gin / gsz) * BN;
-    };
-    auto tile_origin = [&](const int bid, int& m0, int& n0) __attribute__((always_inline)) {
-        const int xcd = bid & 7, idx = bid >> 3;
-        lid_origin((xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx, m0, n0);
-    };
-    // a block whose first index is past the last tile of its XCD's share has nothing to do (idx >= q8 + (xcd < r8))
-    auto has_tile = [&](const int bid) { return (bid >> 3) < q8 + ((bid & 7) < r8 ? 1 : 0); };
 
     const int prow = lane >> 2;
     const int jsrc = (lane & 3) ^ ((prow >> 2) & 3);
@@ -1203,9 +1214,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(c
         char* dst = smem + buf * STAGE + wave * 1024;
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp[i],
-                                             (__attribute__((address_space(3))) void*)(dst + i * (NW * 1024)), 16, 0, 0);
-            gp[i] += TBK * 2;
+            g16_dma_piece(gp[i], dst + i * (NW * 1024));
         }
     };
     const int sw = (l31 >> 2) & 3;
@@ -1213,60 +1222,22 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(c
     const int c0 = ((0 | hf) ^ sw) * 16, c1 = ((2 | hf) ^ sw) * 16;
     f32x16 accM[WM][WN], accX[SINGLE ? 1 : WM][SINGLE ? 1 : WN];      // SINGLE (format 1 operands): the cross terms go into accM
     h8 f0a[2 * WM], f0b[2 * WN], f1a[2 * WM], f1b[2 * WN];
-    auto read_frags = [&](const char* st, const int cs, h8(&fa)[2 * WM], h8(&fb)[2 * WN]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WM; ++i) {
-            fa[i] = *reinterpret_cast<const h8*>(st + a_row + i * 2048 + cs);
-            fa[WM + i] = *reinterpret_cast<const h8*>(st + PA * 1024 + a_row + i * 2048 + cs);
-        }
-#pragma unroll
-        for (int j = 0; j < WN; ++j) {
-            fb[j] = *reinterpret_cast<const h8*>(st + b_row + j * 2048 + cs);
-            fb[WN + j] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_row + j * 2048 + cs);
-        }
-    };
-    constexpr int XMFMA = 0x7ff & ~0x8;
-    auto mfmas = [&](const h8(&fa)[2 * WM], const h8(&fb)[2 * WN]) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[j], accM[i][j], 0, 0, 0);
-        __builtin_amdgcn_sched_barrier(XMFMA);
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j) {
-                if constexpr (SINGLE) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[WN + j], accM[i][j], 0, 0, 0);
-                else accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[i], fb[WN + j], accX[i][j], 0, 0, 0);
-            }
-        __builtin_amdgcn_sched_barrier(XMFMA);
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-            for (int j = 0; j < WN; ++j) {
-                if constexpr (SINGLE) accM[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[WM + i], fb[j], accM[i][j], 0, 0, 0);
-                else accX[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[WM + i], fb[j], accX[i][j], 0, 0, 0);
-            }
-    };
+    const Frag32<WM, WN, PA, PB> frag{a_row, b_row};
+    auto read_frags = [&](const char* st, const int cs, h8(&fa)[2 * WM], h8(&fb)[2 * WN]) __attribute__((always_inline)) { frag.read_frags(st, cs, fa, fb); };
+    auto mfmas = [&](const h8(&fa)[2 * WM], const h8(&fb)[2 * WN]) __attribute__((always_inline)) { frag.template mfmas<SINGLE>(fa, fb, accM, accX); };
     auto read_item = [&](auto rc, const char* st, const int cs, h8(&fa)[2 * WM], h8(&fb)[2 * WN]) __attribute__((always_inline)) {
-        constexpr int R = decltype(rc)::value;
-        if constexpr (R < WM) fa[R] = *reinterpret_cast<const h8*>(st + a_row + R * 2048 + cs);
-        else if constexpr (R < 2 * WM) fa[R] = *reinterpret_cast<const h8*>(st + PA * 1024 + a_row + (R - WM) * 2048 + cs);
-        else if constexpr (R < 2 * WM + WN) fb[R - 2 * WM] = *reinterpret_cast<const h8*>(st + b_row + (R - 2 * WM) * 2048 + cs);
-        else fb[R - 2 * WM] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_row + (R - 2 * WM - WN) * 2048 + cs);
+        frag.template read_item<decltype(rc)::value>(st, cs, fa, fb);
     };
     auto dma_item = [&](auto dc, char* dst) __attribute__((always_inline)) {
         constexpr int I = decltype(dc)::value;
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp[I],
-                                         (__attribute__((address_space(3))) void*)(dst + I * (NW * 1024)), 16, 0, 0);
-        gp[I] += TBK * 2;
+        g16_dma_piece(gp[I], dst + I * (NW * 1024));
     };
 
     int bid = blockIdx.x;
     int pos = 0, pend = 0;           // SK: this block's run of the linear (tile, k-step) space
     int m0, n0;
     if constexpr (SK) {
-        const int T = nblk * ntf, G = gridDim.x;
+        const int T = order.nblk * ntf, G = gridDim.x;
         const int L = (bid & 7) * (G >> 3) + (bid >> 3);
         auto cut = [&](const int l) {
             int x = (int)((long)T * l / G);
@@ -1280,11 +1251,11 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(c
         if (pos >= pend) return;
         const int lid = pos / ntf, k0 = pos - lid * ntf;
         nt = min(pend - pos, ntf - k0);
-        lid_origin(lid, m0, n0);
+        order.lid_origin(lid, m0, n0);
         plan(m0, n0, k0);
     } else {
-        if (!has_tile(bid)) return;
-        tile_origin(bid, m0, n0);
+        if (!order.has_tile(bid)) return;
+        order.tile_origin(bid, m0, n0);
         plan(m0, n0, 0);
     }
 #pragma unroll
@@ -1351,14 +1322,14 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(c
             more = pos < pend;
             if (more) {              // the piece ended at its tile's last k-step: the next one starts a tile
                 nt = min(pend - pos, ntf);
-                lid_origin(pos / ntf, m0, n0);
+                order.lid_origin(pos / ntf, m0, n0);
                 plan(m0, n0, 0);
             }
         } else {
             bid += gridDim.x;
-            more = has_tile(bid);
+            more = order.has_tile(bid);
             if (more) {
-                tile_origin(bid, m0, n0);
+                order.tile_origin(bid, m0, n0);
                 plan(m0, n0, 0);
             }
         }
@@ -1415,19 +1386,16 @@ constexpr int slot_index(int S, int NR, int ND) {
 
 template <int WM, int WN, int NWM, int NWN, int WPS, bool SK, int ACC, bool AKM, bool BKM, int STAGES = 3, bool ONESHOT = false>
 __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, const int g_gm, const int bid0, const int grid) {
-    constexpr int BM = 32 * WM * NWM, BN = 32 * WN * NWN, NW = NWM * NWN;
-    constexpr int PA = BM / 16, PB = BN / 16;
-    constexpr int NP = 2 * PA + 2 * PB;
-    constexpr int STAGE = NP * 1024;
-    constexpr int PPW = NP / NW;
+    using G = RingGeom<WM, WN, NWM, NWN>;
+    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB, STAGE = G::STAGE, PPW = G::PPW;
     constexpr int APW = 2 * PA / NW;                       // this wave's first APW pieces belong to A, the rest to B
     constexpr int RBA = 2 * BM, RBB = 2 * BN;              // bytes per k-row of a k-major plane image
     constexpr int NDA = AKM ? 2 : 1, NDB = BKM ? 2 : 1;    // LDS read instructions per fragment
     constexpr int NIA = 2 * WM * NDA, NIB = 2 * WN * NDB;  // ... per k-step and operand
     constexpr int NRI = NIA + NIB;
-    constexpr int NMF = 3 * WM * WN;
+    constexpr int NMF = G::NMF;
     constexpr int SIDE = NW * 2048;
-    static_assert(NP % NW == 0 && (2 * PA) % NW == 0, "pieces must divide over the waves, operand by operand");
+    static_assert((2 * PA) % NW == 0, "pieces must divide over the waves, operand by operand");
     static_assert(STAGES * STAGE + SIDE <= 160 * 1024, "LDS");
     static_assert(1024 % RBA == 0 && 1024 % RBB == 0, "whole k-rows per DMA piece");
     static_assert(!SK || ACC == 1, "stream-K pieces meet in atomics");
@@ -1437,23 +1405,9 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
     const int wm = wave / NWN, wn = wave % NWN;
     const int l31 = lane & 31, hf = lane >> 5;
     const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
-    const int nblk = nbm * nbn;
     const int ntf = p.K / TBK;                    // k-steps of a whole tile, >= STAGES (host)
     int nt = ntf;
-    const int q8 = nblk >> 3, r8 = nblk & 7;
-    const int gspan = g_gm * nbn;
-    auto lid_origin = [&](const int lid, int& m0, int& n0) __attribute__((always_inline)) {
-        const int gid = lid / gspan, gin = lid - gid * gspan;
-        const int gfirst = gid * g_gm;
-        const int gsz = min(nbm - gfirst, g_gm);
-        m0 = (gfirst + gin % gsz) * BM;
-        n0 = (gin / gsz) * BN;
-    };
-    auto tile_origin = [&](const int bid, int& m0, int& n0) __attribute__((always_inline)) {
-        const int xcd = bid & 7, idx = bid >> 3;
-        lid_origin((xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx, m0, n0);
-    };
-    auto has_tile = [&](const int bid) { return (bid >> 3) < q8 + ((bid & 7) < r8 ? 1 : 0); };
+    const TileOrder<BM, BN> order(nbm, nbn, g_gm);
 
     // ---- DMA plan.  k-contiguous operand: as in the ring kernel (16-row x 64-byte pieces, chunk ^ ((row >> 2) & 3)), gp walks
     // along k.  k-major operand: piece q = k-rows q RPP .. of the tile; lane -> (k-row, physical 16-byte chunk); gp holds the
@@ -1500,11 +1454,8 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
     };
     auto dma_piece = [&](const int i, char* dst) __attribute__((always_inline)) {
         const bool km = (i < APW) ? AKM : BKM;
-        if (!km) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gp[i],
-                                             (__attribute__((address_space(3))) void*)(dst + i * (NW * 1024)), 16, 0, 0);
-            gp[i] += TBK * 2;
-        } else {
+        if (!km) g16_dma_piece(gp[i], dst + i * (NW * 1024));
+        else {
             const int kv = (i < APW) ? ka_valid : kb_valid;
             const int ld = (i < APW) ? p.lda : p.ldb;
             const int krow = min(kt * TBK + prow[i], kv - 1);
@@ -1617,7 +1568,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
     int pos = 0, pend = 0;
     int m0, n0;
     if constexpr (SK) {
-        const int T = nblk * ntf, G = grid;
+        const int T = order.nblk * ntf, G = grid;
         if (p.sk_slices > 0) {
             // ALIGNED k-slices (round 5): the k axis of every tile is cut into S = sk_slices equal slices and a block takes ONE (tile,
             // slice) unit; units are numbered slice-major and dealt to the XCDs in contiguous runs, so the ~G / 8 blocks of an XCD
@@ -1626,7 +1577,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
             // (run l starts at k = 29.25 l mod 96 for fc1's data gradient): nothing is shared, 256 blocks x 1.4 MB = 365 MB come over
             // the fabric for 58 MB of operands (profiles/r04_final_pmc_hbm.txt: 380 MB per launch, 4.9 TB/s -- the kernel was bound by
             // that, not by its MFMAs).
-            const int S = p.sk_slices, U = nblk * S;
+            const int S = p.sk_slices, nblk = order.nblk, U = nblk * S;
             const int xcd = bid & 7, idx = bid >> 3;
             const int ulo = (int)((long)U * xcd / 8), uhi = (int)((long)U * (xcd + 1) / 8);
             if (idx >= uhi - ulo) return;
@@ -1637,7 +1588,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
             nt = min(per, ntf - k0);            // >= 3 for every slice (host)
             pos = lid * ntf + k0;
             pend = pos + nt;
-            lid_origin(lid, m0, n0);
+            order.lid_origin(lid, m0, n0);
             plan(m0, n0, k0);
         } else {
         const int L = (bid & 7) * (G >> 3) + (bid >> 3);
@@ -1653,16 +1604,16 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
         if (pos >= pend) return;
         const int lid = pos / ntf, k0 = pos - lid * ntf;
         nt = min(pend - pos, ntf - k0);
-        lid_origin(lid, m0, n0);
+        order.lid_origin(lid, m0, n0);
         plan(m0, n0, k0);
         }
     } else if constexpr (ONESHOT) {
-        if (bid >= nblk) return;             // grouped launch: bid0 IS the tile's position in this problem's grouped order
-        lid_origin(bid, m0, n0);
+        if (bid >= order.nblk) return;       // grouped launch: bid0 IS the tile's position in this problem's grouped order
+        order.lid_origin(bid, m0, n0);
         plan(m0, n0, 0);
     } else {
-        if (!has_tile(bid)) return;
-        tile_origin(bid, m0, n0);
+        if (!order.has_tile(bid)) return;
+        order.tile_origin(bid, m0, n0);
         plan(m0, n0, 0);
     }
 #pragma unroll
@@ -1735,16 +1686,16 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
             more = pos < pend;
             if (more) {
                 nt = min(pend - pos, ntf);
-                lid_origin(pos / ntf, m0, n0);
+                order.lid_origin(pos / ntf, m0, n0);
                 plan(m0, n0, 0);
             }
         } else if constexpr (ONESHOT) {
             more = false;                 // one tile per block (grouped launch): no next-tile state to carry through the epilogue
         } else {
             bid += grid;
-            more = has_tile(bid);
+            more = order.has_tile(bid);
             if (more) {
-                tile_origin(bid, m0, n0);
+                order.tile_origin(bid, m0, n0);
                 plan(m0, n0, 0);
             }
         }
@@ -1828,23 +1779,37 @@ extern "C" int dupl_split_f16x2b(const float* x, void* hi, void* lo, int64_t n, 
     return dupl_launch_status();
 }
 
+// What dupl_gemm_f16x3 and dupl_gemm_f16x3_group require of a descriptor alike: the operands and their layout.  (Each entry point adds
+// its own conditions on the outputs, the epilogue and the launch tuning.)
+static bool g16_operands_ok(const dupl_gemm16_desc& d) {
+    if (d.struct_size != sizeof(dupl_gemm16_desc)) return false;      // a caller built against another header
+    if (!d.A_hi || !d.A_lo || !d.B_hi || !d.B_lo || d.M <= 0 || d.N <= 0 || d.K <= 0) return false;
+    if ((d.K % TBK) || (d.lda % 8) || (d.ldb % 8)) return false;       // whole 16-byte chunks, whole k-tiles
+    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    if (!al16(d.A_hi) || !al16(d.A_lo) || !al16(d.B_hi) || !al16(d.B_lo)) return false;
+    if (d.group < 0 || d.group > 4096) return false;
+    if (d.a_layout < 0 || d.a_layout > 1 || d.b_layout < 0 || d.b_layout > 1 || d.ka_valid < 0 || d.kb_valid < 0) return false;
+    if (d.a_layout || d.b_layout) {
+        // k-major operand(s): format 1 planes, the 3-stage prologue, whole 16-byte chunks of rows, k_valid of a k-major operand only
+        if (d.fmt != 1 || d.K / TBK < 3) return false;
+        if ((d.a_layout && (d.M & 7)) || (d.b_layout && (d.N & 7))) return false;
+        if (d.ka_valid > d.K || d.kb_valid > d.K) return false;
+        if ((!d.a_layout && d.ka_valid) || (!d.b_layout && d.kb_valid)) return false;
+    }
+    return true;
+}
+
 extern "C" int dupl_gemm_f16x3_group(const dupl_gemm16_desc* descs, int32_t n, dupl_stream_t stream) {
     if (!descs || n < 1 || n > DUPL_GEMM16_GROUP_MAX) return DUPL_ERR_ARG;
     g16_group_args g;
     g.n = n;
     int total = 0, group = 0;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     for (int i = 0; i < n; ++i) {
         const dupl_gemm16_desc& d = descs[i];
-        if (d.struct_size != sizeof(dupl_gemm16_desc)) return DUPL_ERR_ARG;
-        if (!d.A_hi || !d.A_lo || !d.B_hi || !d.B_lo || !d.C || d.C_hi || d.C_lo || d.bias || d.res || d.c_rows || d.amax_out ||
-            d.M <= 0 || d.N <= 0 || d.K <= 0)
-            return DUPL_ERR_ARG;
-        if (d.flags != DUPL_GEMM_ACCUM || d.fmt != 1 || d.a_layout != 1 || d.b_layout != 1 || (d.K % TBK) || d.K / TBK < 3 ||
-            (d.lda % 8) || (d.ldb % 8) || (d.M & 7) || (d.N & 7) || d.ka_valid < 0 || d.kb_valid < 0 || d.ka_valid > d.K ||
-            d.kb_valid > d.K || d.group < 0 || d.group > 4096)
-            return DUPL_ERR_ARG;
-        if (!al16(d.A_hi) || !al16(d.A_lo) || !al16(d.B_hi) || !al16(d.B_lo)) return DUPL_ERR_ARG;
+        if (!g16_operands_ok(d)) return DUPL_ERR_ARG;
+        // a weight gradient on the forward's planes: C += alpha A^T . B, both operands k-major, nothing else
+        if (d.flags != DUPL_GEMM_ACCUM || d.a_layout != 1 || d.b_layout != 1) return DUPL_ERR_ARG;
+        if (!d.C || d.C_hi || d.C_lo || d.bias || d.res || d.c_rows || d.amax_out) return DUPL_ERR_ARG;
         g.d[i] = d;
         g.first[i] = total;
         const int nblk = ((d.M + 255) / 256) * ((d.N + 127) / 128);
@@ -1877,23 +1842,32 @@ static bool g16_split_rows(const dupl_gemm16_desc& d, const int M1, dupl_gemm16_
     return d2.C || d2.C_hi;
 }
 
+// dupl_gemm16_desc.tile: the codes dupl_gemm_f16x3 accepts
+constexpr int G16_TILES[] = {
+    0,    // the launcher's choice
+    3,    // gemm_f16x3_kernel, 128 x 64 on 4 waves; format 0, split-K
+    5,    // gemm_f16x3_kernel, 128 x 128 on 8 waves; format 0, split-K
+    6,    // gemm_f16x3_ring_kernel, 256 x 128 on 8 waves; format 0, one block per tile
+    7,    // gemm_f16x3_ring_kernel, 256 x 128 on 4 waves; format 0, one block per tile
+    8,    // gemm_f16x3_ring_kernel SINGLE, 256 x 256 on 8 waves; format 1, one block per tile
+    10,   // gemm_f16x3_pring_kernel, 256 x 128; format 0, persistent
+    11,   // gemm_f16x3_pring_kernel SK, 256 x 128; format 0, stream-K for DUPL_GEMM_ACCUM
+    12,   // gemm_f16x3_ring_kernel SINGLE, 256 x 128; format 1, one block per tile
+    14,   // gemm_f16x3_pring_kernel SINGLE, 256 x 128; format 1, persistent
+    18,   // gemm_f16x3_ring16_kernel, 256 x 256; format 1 on the 16x16x32 MFMA, one block per tile
+    22,   // gemm_f16x3_ring16_kernel, 256 x 128; format 1 on the 16x16x32 MFMA, one block per tile
+};
+
 extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) {
-    if (!d || d->struct_size != sizeof(dupl_gemm16_desc)) return DUPL_ERR_ARG;      // a caller built against another header
-    if (!d->A_hi || !d->A_lo || !d->B_hi || !d->B_lo || d->M <= 0 || d->N <= 0 || d->K <= 0) return DUPL_ERR_ARG;
-    if ((d->K % TBK) || (d->lda % 8) || (d->ldb % 8)) return DUPL_ERR_ARG;       // whole 16-byte chunks, whole k-tiles
-    if (d->tile < 0 || d->concurrency < 0 || d->concurrency > 8 || d->group < 0 || d->group > 4096 || d->persist_blocks < 0 ||
-        d->persist_blocks > 1024 || (d->persist_blocks & 7))
+    if (!d || !g16_operands_ok(*d)) return DUPL_ERR_ARG;
+    if (d->concurrency < 0 || d->concurrency > 8 || d->persist_blocks < 0 || d->persist_blocks > 1024 || (d->persist_blocks & 7))
         return DUPL_ERR_ARG;
-    {
-        const int t = d->tile;
-        if (t != 0 && t != 3 && t != 5 && t != 6 && t != 7 && t != 8 && t != 10 && t != 11 && t != 12 && t != 14 && t != 18 && t != 22) return DUPL_ERR_ARG;
-    }
+    bool known_tile = false;
+    for (const int t : G16_TILES) known_tile |= d->tile == t;
+    if (!known_tile) return DUPL_ERR_ARG;
     const int g16_tile = d->tile, g16_concurrency = d->concurrency > 0 ? d->concurrency : 1;
     const int g16_persist_blocks = d->persist_blocks ? d->persist_blocks : (g16_concurrency >= 2 ? 192 : 256);
     const int g16_group_m = d->group ? d->group : G16_GROUP_M, g16_group_ring = d->group ? d->group : G16_GROUP_RING;
-    const int g16_f1_big_from = G16_F1_BIG_FROM;
-    auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if (!al16(d->A_hi) || !al16(d->A_lo) || !al16(d->B_hi) || !al16(d->B_lo)) return DUPL_ERR_ARG;
     if (!d->C && !d->C_hi) return DUPL_ERR_ARG;
     if ((d->C_hi == nullptr) != (d->C_lo == nullptr)) return DUPL_ERR_ARG;
     if ((d->flags & (DUPL_GEMM_STORE_PRE | DUPL_GEMM_MUL_DGELU | DUPL_GEMM_MUL_RELUMASK)) && !d->aux) return DUPL_ERR_ARG;
@@ -1939,20 +1913,16 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         else tile = b128 < 200 ? 3 : 5;
     }
     auto blocks = [&](int bm, int bn) { return dim3((unsigned)(((d->M + bm - 1) / bm) * ((d->N + bn - 1) / bn)), (unsigned)ksplit); };
-    // grid of a persistent kernel: every block walks the same number of tiles (see tile 10 below)
+    // grid of a persistent kernel, every block walks the same number of tiles: with tx tiles per XCD and at most maxb / 8 blocks per
+    // XCD the walk takes rounds = ceil(tx / (maxb / 8)) tiles, and ceil(tx / rounds) blocks per XCD are enough for that -- 600 tiles
+    // run as 3 x 200 instead of 2.3 x 256 (the kernel is power-bound: a few CUs less cost nothing, an idle last round does)
     auto persist_grid = [&](const int nblk) {
         const int tx = (nblk + 7) / 8, bmax = g16_persist_blocks / 8;
         const int rounds = (tx + bmax - 1) / bmax;
         return dim3((unsigned)(8 * ((tx + rounds - 1) / rounds)));
     };
-    if (d->a_layout < 0 || d->a_layout > 1 || d->b_layout < 0 || d->b_layout > 1 || d->ka_valid < 0 || d->kb_valid < 0) return DUPL_ERR_ARG;
-    if (d->a_layout || d->b_layout) {
+    if (kmajor) {
         // k-major operand(s): the backward GEMMs on the forward's own planes (gemm_f16x3_km_kernel; 256 x 128, persistent)
-        if (d->fmt != 1 || d->K / TBK < 3) return DUPL_ERR_ARG;
-        if ((d->a_layout && ((d->M & 7) || d->M < 8)) || (d->b_layout && ((d->N & 7) || d->N < 8))) return DUPL_ERR_ARG;
-        if ((d->a_layout ? d->ka_valid : 0) > d->K || (d->b_layout ? d->kb_valid : 0) > d->K) return DUPL_ERR_ARG;
-        if (!d->a_layout && d->ka_valid) return DUPL_ERR_ARG;
-        if (!d->b_layout && d->kb_valid) return DUPL_ERR_ARG;
         const int nb21 = ((d->M + 255) / 256) * ((d->N + 127) / 128);
         const bool sk = accum && !d->deterministic && ksplit > 1;
         // stream-K forms: aligned k-slices (dupl_gemm16_desc.sk_slices: 0 = as many slices per tile as the grid has blocks for, every
@@ -2006,7 +1976,7 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         // (18 / 22: the same two tiles on the 16x16x32 MFMA, gemm_f16x3_ring16_kernel; the launcher's own choice, since the clock the
         // chip holds under this loop is higher on that shape.  Both tiles switch together: they are bit-identical to each other)
         int t = (g16_tile == 8 || g16_tile == 12 || g16_tile == 14 || g16_tile == 18 || g16_tile == 22) ? g16_tile
-                                                                                                         : (nb22 >= g16_f1_big_from ? 18 : 22);
+                                                                                                         : (nb22 >= G16_F1_BIG_FROM ? 18 : 22);
         if (d->K / TBK < 3 && t == 14) t = 12;
         if (t == 18) {
             // One block per CU and launch: nb22 tiles take ceil(nb22 / 256) rounds, and a last round that holds a few tiles costs as
@@ -2042,17 +2012,11 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         return dupl_launch_status();
     }
     if (tile == 10) {
-        // every block walks the same number of tiles: with tx tiles per XCD and at most maxb / 8 blocks per XCD the walk takes
-        // rounds = ceil(tx / (maxb / 8)) tiles, and ceil(tx / rounds) blocks per XCD are enough for that -- 600 tiles run as
-        // 3 x 200 instead of 2.3 x 256 (the kernel is power-bound: a few CUs less cost nothing, an idle last round does)
-        const int nblk = ((d->M + 255) / 256) * ((d->N + 127) / 128);
-        const int tx = (nblk + 7) / 8, bmax = g16_persist_blocks / 8;
-        const int rounds = (tx + bmax - 1) / bmax;
-        const int grid = 8 * ((tx + rounds - 1) / rounds);
-        DUPL_LAUNCH((gemm_f16x3_pring_kernel<2, 2, 4, 2, 2>), dim3((unsigned)grid), dim3(512), 0, s, *d, g16_group_ring);
+        DUPL_LAUNCH((gemm_f16x3_pring_kernel<2, 2, 4, 2, 2>), persist_grid(((d->M + 255) / 256) * ((d->N + 127) / 128)), dim3(512), 0, s, *d,
+                    g16_group_ring);
         return dupl_launch_status();
     }
-    if (tile == 8 || tile == 9 || tile == 12 || tile == 14 || tile == 18 || tile == 22) tile = 5;      // single-accumulator tiles: format 1 operands only (above)
+    if (tile == 8 || tile == 12 || tile == 14 || tile == 18 || tile == 22) tile = 5;      // single-accumulator tiles: format 1 operands only (above)
     if (tile == 6) DUPL_LAUNCH((gemm_f16x3_ring_kernel<2, 2, 4, 2, 2>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
     else if (tile == 7) DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 2, 1>), blocks(256, 128), dim3(256), 0, s, *d, g16_group_ring);
     else if (tile == 3) DUPL_LAUNCH((gemm_f16x3_kernel<2, 1, 2, 2, 2>), blocks(128, 64), dim3(256), 0, s, *d, g16_group_m);

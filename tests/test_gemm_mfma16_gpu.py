@@ -158,3 +158,131 @@ def test_mfma16_element_wise_store_path(dev, tile):
     e16, e32 = float((y.double() - want).abs().max()) / sc, float((y32.double() - want).abs().max()) / sc
     print(f"{M}x{N}x{K} tile {tile}: 16x16x32 {e16:.2e}  f32 {e32:.2e}")
     assert e16 <= 2.0 * e32 + 1e-7
+
+
+# ------------------------------------------------------------------------------------------ the launchers' argument checks
+def _refusal_bases(dev):
+    """Four valid 64 x 64 x 96 descriptors, every destination NaN-filled: f1 = format 1, k-contiguous, bias + planes out (the forward);
+    f0 = the same on format 0 planes; dgrad = f1 with a k-major B; wgrad = format 1, both operands k-major, C += (what the group
+    entry point takes)."""
+    from dupl_amd import ops, _lib
+    M = N = 64
+    K = 96
+    g = torch.Generator().manual_seed(96)
+    x, xt = torch.randn(M, K, generator=g).to(dev), torch.randn(K, M, generator=g).to(dev)
+    keep = dict(x1=ops.split16(x, exp=ops.EXP_ACT), x0=ops.split16(x), xt1=ops.split16(xt, exp=ops.EXP_ACT),
+                bias=torch.zeros(N, device=dev), C=_nan(M, N), aux=_nan(M, N), o1=_planes_nan(M, N, ops.EXP_ACT), o0=_planes_nan(M, N, 0))
+
+    def desc(a, b, lda, out16):
+        d = _lib.Gemm16Desc()
+        d.A_hi, d.A_lo, d.B_hi, d.B_lo = a.hi, a.lo, b.hi, b.lo
+        d.C = keep["C"].data_ptr()
+        if out16 is not None:
+            d.C_hi, d.C_lo, d.out_exp = out16.hi, out16.lo, out16.exp
+        d.M, d.N, d.K = M, N, K
+        d.lda = d.ldb = lda
+        d.ldc = d.ldo = d.ldaux = N
+        d.fmt = a.fmt
+        d.post_scale = 2.0 ** -(a.exp + b.exp)
+        return d
+
+    f1, f0 = desc(keep["x1"], keep["x1"], K, keep["o1"]), desc(keep["x0"], keep["x0"], K, keep["o0"])
+    dgrad, wgrad = desc(keep["x1"], keep["xt1"], K, keep["o1"]), desc(keep["xt1"], keep["xt1"], M, None)
+    dgrad.ldb, dgrad.b_layout = N, 1
+    wgrad.flags, wgrad.a_layout, wgrad.b_layout = _lib.GEMM_ACCUM, 1, 1
+    for d in (f1, f0, dgrad):
+        d.bias, d.aux = keep["bias"].data_ptr(), keep["aux"].data_ptr()
+    return dict(f1=f1, f0=f0, dgrad=dgrad, wgrad=wgrad), keep
+
+
+def _set(**fields):
+    def edit(d, keep):
+        for k, v in fields.items():
+            setattr(d, k, v(d, keep) if callable(v) else v)
+    return edit
+
+
+def _flag(name):
+    """dupl_amd._lib.<name>, looked up when the case runs."""
+    def get(d, keep):
+        from dupl_amd import _lib
+        return getattr(_lib, name)
+    return get
+
+
+_ACCUM, _PRE = _flag("GEMM_ACCUM"), _flag("GEMM_STORE_PRE")
+# case -> (base descriptor, the edit that breaks it).  More than one field is set only where the broken one cannot be reached otherwise:
+# the accumulating cases drop what ACCUM does not take besides the field in question.
+GEMM16_REFUSALS = {
+    "struct_size": ("f1", _set(struct_size=lambda d, k: d.struct_size + 8)),
+    "K100": ("f1", _set(K=100)),
+    "lda100": ("f1", _set(lda=100)),
+    "A_hi-plus-2-bytes": ("f1", _set(A_hi=lambda d, k: d.A_hi + 2)),
+    "tile4": ("f1", _set(tile=4)),
+    "tile9": ("f1", _set(tile=9)),
+    "persist_blocks12": ("f1", _set(persist_blocks=12)),
+    "concurrency9": ("f1", _set(concurrency=9)),
+    "no-C-no-C_hi": ("f1", _set(C=None, C_hi=None, C_lo=None)),
+    "C_hi-without-C_lo": ("f1", _set(C_lo=None)),
+    "store_pre-without-aux": ("f1", _set(flags=_PRE, aux=None)),
+    "unknown-flag": ("f1", _set(flags=1 << 12)),
+    "accum-with-bias": ("f0", _set(flags=_ACCUM, C_hi=None, C_lo=None)),
+    "fmt2": ("f1", _set(fmt=2)),
+    "out_exp3-fmt0": ("f0", _set(out_exp=3)),
+    "fmt1-kcontig-accum": ("f1", _set(flags=_ACCUM, C_hi=None, C_lo=None, bias=None)),
+    "a_layout-fmt0": ("f0", _set(a_layout=1, lda=64)),
+    "b_layout-N60": ("dgrad", _set(N=60)),
+    "kmajor-K64": ("dgrad", _set(K=64)),
+    "ka_valid-without-a_layout": ("dgrad", _set(ka_valid=64)),
+    "group-n0": ("wgrad", _set()),
+    "group-n-above-max": ("wgrad", _set()),
+    "group-flags0": ("wgrad", _set(flags=0)),
+    "group-fmt0": ("wgrad", _set(fmt=0)),
+}
+
+
+@pytest.mark.parametrize("case", list(GEMM16_REFUSALS))
+def test_gemm16_launchers_refuse_bad_descriptors(dev, case):
+    """dupl_gemm_f16x3 / dupl_gemm_f16x3_group answer every broken descriptor with status -1 from a check that precedes the launch:
+    C, aux and the result planes keep their NaN fill."""
+    import ctypes
+    from dupl_amd import ops, _lib
+    bases, keep = _refusal_bases(dev)
+    base, edit = GEMM16_REFUSALS[case]
+    d = bases[base]
+    edit(d, keep)
+    if case.startswith("group-"):
+        n = {"group-n0": 0, "group-n-above-max": _lib.GEMM16_GROUP_MAX + 1}.get(case, 1)
+        arr = (_lib.Gemm16Desc * max(n, 1))(*([d] * max(n, 1)))
+
+        def call():
+            ops.L().dupl_gemm_f16x3_group(arr, n, ops._stream())
+    else:
+        def call():
+            ops.L().dupl_gemm_f16x3(ctypes.byref(d), ops._stream())
+    with pytest.raises(RuntimeError, match="status -1"):
+        call()
+    torch.cuda.synchronize()
+    for name in ("C", "aux"):
+        assert bool(torch.isnan(keep[name]).all()), f"{case}: {name} was written"
+    for name in ("o1", "o0"):
+        assert bool(torch.isnan(keep[name].planes).all()), f"{case}: planes {name} were written"
+
+
+def test_gemm16_refusal_bases_are_accepted(dev):
+    """The descriptors the refusal cases start from are valid: each launches (status 0) and overwrites its NaN-filled C."""
+    import ctypes
+    from dupl_amd import ops, _lib
+    for name in ("f1", "f0", "dgrad", "wgrad", "group"):
+        bases, keep = _refusal_bases(dev)
+        d = bases["wgrad" if name == "group" else name]
+        if d.flags & _lib.GEMM_ACCUM:
+            keep["C"].zero_()
+        if name == "group":
+            ops.L().dupl_gemm_f16x3_group((_lib.Gemm16Desc * 1)(d), 1, ops._stream())
+        else:
+            ops.L().dupl_gemm_f16x3(ctypes.byref(d), ops._stream())
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(keep["C"]).all()), name
+        if not d.flags & _lib.GEMM_ACCUM:
+            assert bool(torch.isfinite(keep["o0" if name == "f0" else "o1"].planes.float()).all()), name

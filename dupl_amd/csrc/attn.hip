@@ -11,7 +11,7 @@
 // lane's Q fragment is a contiguous 128-byte run.
 //
 // qkv is the raw nn.Linear(dim, 3*dim) output [B*N][3*H*HD] (vit.py:122); out is [B*N][H*HD].
-#include "common.h"
+#include "split_frag.h"      // fast_exp, xcd_remap3
 #include "../../include/dupl_hip.h"
 
 namespace {
@@ -22,11 +22,6 @@ constexpr int ANT = 256;  // threads: 4 waves x 32 rows
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
 
 __device__ __forceinline__ int acc_row(int e, int hf) { return (e & 3) + 8 * (e >> 2) + 4 * hf; }
-
-// exp for the softmax: one v_exp_f32 on x*log2(e) instead of libm expf's ~18-instruction sequence.  Arguments are
-// (score - running max) in [-inf, 0]; the result's relative error is ~1e-6 (|x| * 2^-24 from the scaled argument +
-// 1 ulp of v_exp_f32), the same class as the fp32 round-off of the surrounding sums (tests: 5e-6 vs fp64).
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 
 // Stage a (KT x HD) tile (rows r0.., row stride ld floats) into registers; rows >= R are zero.
 template <int HD>
@@ -62,23 +57,6 @@ __device__ __forceinline__ void load_rowfrag(float (&f)[HD / 2], const float* __
         float4 v = valid ? *reinterpret_cast<const float4*>(rowp + 4 * i) : make_float4(0.f, 0.f, 0.f, 0.f);
         f[4 * i + 0] = v.x * mul; f[4 * i + 1] = v.y * mul; f[4 * i + 2] = v.z * mul; f[4 * i + 3] = v.w * mul;
     }
-}
-
-// Workgroups are dealt round-robin to the 8 XCDs in linear (x, y, z) order, so the ceil(N/128) blocks that share one
-// head's K / V would each pull them into a different XCD's L2.  Same bijective band remap as the GEMM: XCD x owns a
-// contiguous run of (query-block, head, image) work items, i.e. whole heads.
-__device__ __forceinline__ void xcd_remap3(int remap, int& bx, int& by, int& bz) {
-    bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
-    if (!remap) return;
-    const int gx = gridDim.x, gy = gridDim.y;
-    const int total = gx * gy * gridDim.z;
-    const int L = bx + gx * (by + gy * bz);
-    const int q = total >> 3, r = total & 7;
-    const int xcd = L & 7, idx = L >> 3;
-    const int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    bx = w % gx;
-    by = (w / gx) % gy;
-    bz = w / (gx * gy);
 }
 
 // ------------------------------------------------------------------------------------------------ forward

@@ -14,8 +14,7 @@
 // [8 keys][32 d] (the layout of gemm_split.hip's k-major operands) and ds_read_b64_tr_b16 gathers the fragments, so no
 // transposed copy of V is ever written (rounds 2-3 ran a vt_planes kernel per call: 0.7 ms / step).
 // Block = 4 waves x 32 queries, 64 keys per iteration, two LDS stages (64 KB, 2 blocks / CU), one barrier per key tile.
-#include "common.h"
-#include <type_traits>
+#include "split_frag.h"
 #include "../../include/dupl_hip.h"
 
 #ifndef ATT_PRIO
@@ -27,38 +26,9 @@
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
-constexpr float LO_INV = 1.f / DUPL_LO_SCALE;
 constexpr int HD = 64, KT = 64;
 constexpr int PLANE = KT * 128;          // one [64][128 B] image
 constexpr int STAGE = 4 * PLANE;         // K_hi | K_lo | V_hi | V_lo
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-
-__device__ __forceinline__ void xcd_remap3(int remap, int& bx, int& by, int& bz) {
-    bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
-    if (!remap) return;
-    const int gx = gridDim.x, gy = gridDim.y;
-    const int total = gx * gy * gridDim.z;
-    const int L = bx + gx * (by + gy * bz);
-    const int q = total >> 3, r = total & 7;
-    const int xcd = L & 7, idx = L >> 3;
-    const int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    bx = w % gx;
-    by = (w / gx) % gy;
-    bz = w / (gx * gy);
-}
 
 // Several batches of one token buffer in ONE launch (round 5).  The ms-CAM pass of a step holds three batches of different length
 // (8 x 785, 8 x 197, 8 x 1 765 tokens at 448^2, 4 images); a launch per batch is 672 / 192 / 1 344 blocks for the chip's 512 block
@@ -90,12 +60,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
         const int gx = (N + 127) / 128;
         const int G = gx * H * segs.B[sg];
         const int L = (int)blockIdx.x - segs.first[sg];
-        int w = L;
-        if (remap) {                  // whole heads per XCD inside the segment (xcd_remap3 on the segment's own index)
-            const int q = G >> 3, r = G & 7;
-            const int xcd = L & 7, idx = L >> 3;
-            w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        }
+        const int w = remap ? xcd_band(L, G) : L;      // whole heads per XCD inside the segment
         bx = w % gx; h = (w / gx) % H; b = w / (gx * H);
     }
     {
@@ -115,13 +80,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
         const size_t off = ((size_t)b * N + min(qrow, N - 1)) * ld + h * HD + 8 * hf;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            qh[s] = *reinterpret_cast<const h8*>(qkv_hi + off + 16 * s);
-            ql[s] = *reinterpret_cast<const h8*>(qkv_lo + off + 16 * s);
+            qh[s] = load_bfrag(qkv_hi + off, s);
+            ql[s] = load_bfrag(qkv_lo + off, s);
         }
     }
 
     // ---- DMA plan: piece g = wave + 4 i covers rows 8 q .. 8 q + 7 (q = wave + 4 (i & 1)) of plane i / 2
-    const int prow = lane >> 3, pch = lane & 7;
+    const int prow = lane >> 3;
     const char* kbase[2];      // K planes at this (b, h): row 0, column chunk 0
     kbase[0] = reinterpret_cast<const char*>(qkv_hi + (size_t)b * N * ld + D + h * HD);
     kbase[1] = reinterpret_cast<const char*>(qkv_lo + (size_t)b * N * ld + D + h * HD);
@@ -129,17 +94,14 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
     vbase[0] = kbase[0] + D * 2;
     vbase[1] = kbase[1] + D * 2;
     int krow[2], kch[2], vrow[2];
-    // V piece q = wave + 4 j (1 KB = subtiles 2 q, 2 q + 1 = key group q, d blocks 0 / 1): lane -> subtile row (lane >> 2) & 7,
-    // 16-byte chunk lane & 3 of d block lane >> 5; key group q holds keys 16 (q >> 1) + 4 (q & 1) + {0..3, 8..11} in rows 0 .. 7
-    const int vch = ((lane >> 5) * 32 + (lane & 3) * 8) * 2;
+    const int vch = km_piece_col_bytes(lane);                   // V piece q = wave + 4 j, k-major (subtile layout: split_frag.h)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int r = 8 * (wave + 4 * j) + prow;                 // tile row of this lane in pieces with (i & 1) == j
-        const int c = pch ^ ((r >> 1) & 7);                      // source chunk (swizzle on the source side)
+        const int r = 8 * (wave + 4 * j) + prow;                 // row of this lane in row-major piece wave + 4 j (split_frag.h)
         krow[j] = r;
-        kch[j] = c * 16;
+        kch[j] = rm_piece_col_bytes(lane, r);
         const int q = wave + 4 * j, srow = (lane >> 2) & 7;
-        vrow[j] = (q >> 1) * 16 + (srow >> 2) * 8 + (q & 1) * 4 + (srow & 3);
+        vrow[j] = (q >> 1) * 16 + (srow >> 2) * 8 + (q & 1) * 4 + (srow & 3);      // mirrors km_piece_row(wave + 4 * j, lane)
     }
     // a piece's source = (uniform) plane base of tile t + a 32-bit per-lane offset (the planes of one call are far below 4 GB): the
     // DMA takes the base in scalar registers, 4 vector registers hold the offsets.  A whole tile (all 64 keys < N) uses the
@@ -152,36 +114,31 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
         koff[j] = (unsigned)krow[j] * (unsigned)(ld * 2) + kch[j];
         voff[j] = (unsigned)vrow[j] * (unsigned)(ld * 2) + vch;
     }
-    auto dma16 = [](const char* ubase, const unsigned off, char* dst) __attribute__((always_inline)) {
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(ubase + off),
-                                         (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-    };
+    auto dma16o = [](const char* ubase, const unsigned off, char* dst) __attribute__((always_inline)) { dma16(ubase + off, dst); };
     auto issue = [&](int t, int buf) __attribute__((always_inline)) {
         char* dst = smem + buf * STAGE + wave * 1024;
         const size_t o = t * tstride;
         if (t * KT + KT <= N) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dma16(kbase[i >> 1] + o, koff[i & 1], dst + i * 4096);
+            for (int i = 0; i < 4; ++i) dma16o(kbase[i >> 1] + o, koff[i & 1], dst + i * 4096);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dma16(vbase[i >> 1] + o, voff[i & 1], dst + (4 + i) * 4096);
+            for (int i = 0; i < 4; ++i) dma16o(vbase[i >> 1] + o, voff[i & 1], dst + (4 + i) * 4096);
         } else {
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                dma16(kbase[i >> 1] + o, (unsigned)(min(t * KT + krow[i & 1], N - 1) - t * KT) * (unsigned)(ld * 2) + kch[i & 1], dst + i * 4096);
+                dma16o(kbase[i >> 1] + o, (unsigned)(min(t * KT + krow[i & 1], N - 1) - t * KT) * (unsigned)(ld * 2) + kch[i & 1], dst + i * 4096);
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                dma16(vbase[i >> 1] + o, (unsigned)(min(t * KT + vrow[i & 1], N - 1) - t * KT) * (unsigned)(ld * 2) + vch, dst + (4 + i) * 4096);
+                dma16o(vbase[i >> 1] + o, (unsigned)(min(t * KT + vrow[i & 1], N - 1) - t * KT) * (unsigned)(ld * 2) + vch, dst + (4 + i) * 4096);
         }
     };
 
     // ---- fragment addresses
     // K (A operand of S^T): MFMA row l31 <- key pi(l31) of the 32-key sub-tile; chunk (2 s + hf) ^ ((row >> 1) & 7)
-    const int g4 = (l31 >> 2) & 3;
-    const int krow_a = (l31 & ~12) | ((g4 == 1 ? 2 : (g4 == 2 ? 1 : g4)) << 2);
+    const int krow_a = pi_row(l31);
     const int k_off = krow_a * 128, k_sw = (krow_a >> 1) & 7;
-    // V (k-major A operand of O^T): lane (g = lane >> 4, q = lane & 15) of the read (key step sg, half jj, d block dd) takes subtile
-    // row (g >> 1) * 4 + (q >> 2), d 16 (g & 1) + 4 (q & 3) .. + 3 of subtile (sg * 2 + jj) * 2 + dd; the reads are inline asm (a
-    // builtin read behind an LDS-DMA makes hipcc drain vmcnt first, gemm_split.hip) with explicit lgkmcnt waits at the consumers
+    // V (k-major A operand of O^T): the read (key step sg, half jj, d block dd) takes subtile (sg * 2 + jj) * 2 + dd by km_tr_read,
+    // with explicit lgkmcnt waits at the consumers (split_frag.h); the lane offset mirrors km_read_lane_off(lane)
     const int vg = lane >> 4, vq = lane & 15;
     const unsigned v_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem) + 2 * PLANE +
                            ((vg >> 1) * 4 + (vq >> 2)) * 64 + (16 * (vg & 1) + 4 * (vq & 3)) * 2;
@@ -251,16 +208,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
         // the first V^T fragments are fetched now: their LDS latency hides under the softmax arithmetic
         h4 vf[2][8];                         // [set][(plane * 2 + d block) * 2 + half]
         const unsigned v_st = v_lds + (t & 1) * STAGE;
-        auto tr_read = [](const unsigned addr, auto offc) __attribute__((always_inline)) {
-            h4 v;
-            asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(decltype(offc)::value) : "memory");
-            return v;
-        };
         auto v_read = [&](auto sgc, h4(&f)[8]) __attribute__((always_inline)) {
             constexpr int SG = decltype(sgc)::value;
             static_for<8>([&](auto ic) __attribute__((always_inline)) {
                 constexpr int i = decltype(ic)::value, pl = i >> 2, dd = (i >> 1) & 1, jj = i & 1;
-                f[i] = tr_read(v_st, std::integral_constant<int, pl * PLANE + ((SG * 2 + jj) * 2 + dd) * 512>{});
+                f[i] = km_tr_read<pl * PLANE + ((SG * 2 + jj) * 2 + dd) * 512>(v_st);
             });
         };
         v_read(std::integral_constant<int, 0>{}, vf[0]);
@@ -272,9 +224,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
         // the cross terms move a score by <= 2^-11 of its size, and softmax does not care which constant near the maximum is
         // subtracted as long as numerator, denominator and lse use the same one); (ii) score scaling, cross-term fold and the
         // subtraction of the maximum are two packed FMAs on accumulator pairs feeding exp2 directly; (iii) the hi / lo split of
-        // P is one packed convert, one packed multiply and one mixed-precision FMA per element: lo = f16(fma(f32(hi), -2048,
-        // 2048 p)) -- the same value as f16((p - hi) * 2048) (every step exact up to the final rounding), with hi read back from
-        // the register that is used as the operand, so hi and lo cannot disagree.
+        // P is split_pair (split_frag.h): one packed convert, one packed multiply and one mixed-precision FMA per element.
         if (t == nkt - 1) {            // block-uniform: keys >= N exist in the last tile only
             const int kbase_t = t * KT + 8 * hf;
 #pragma unroll
@@ -309,7 +259,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
         const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);                     // exactly 1 when the maximum stays
         f32x2 psum2 = {0.f, 0.f};
         h8 ph[4], pl[4];
-        typedef _Float16 h2v __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int kt2 = 0; kt2 < 2; ++kt2)
 #pragma unroll
@@ -318,13 +267,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
                 const f32x2 v2 = __builtin_elementwise_fma(x2, f32x2{c2, c2}, __builtin_elementwise_fma(m2, f32x2{c1, c1}, f32x2{-m_new, -m_new}));
                 const f32x2 p2 = {__builtin_amdgcn_exp2f(v2[0]), __builtin_amdgcn_exp2f(v2[1])};
                 psum2 += p2;
-                const h2v hh = __builtin_convertvector(p2, h2v);                 // v_cvt_pk_f16_f32 (round to nearest even)
-                const f32x2 q2 = p2 * f32x2{DUPL_LO_SCALE, DUPL_LO_SCALE};
-                const int idx = 2 * kt2 + (e >> 3);
-                ph[idx][e & 7] = hh[0];
-                ph[idx][(e & 7) + 1] = hh[1];
-                pl[idx][e & 7] = (_Float16)__builtin_fmaf((float)hh[0], -DUPL_LO_SCALE, q2[0]);
-                pl[idx][(e & 7) + 1] = (_Float16)__builtin_fmaf((float)hh[1], -DUPL_LO_SCALE, q2[1]);
+                split_pair(p2, ph[2 * kt2 + (e >> 3)], pl[2 * kt2 + (e >> 3)], e & 7);
             }
         const float psum = psum2[0] + psum2[1];
         l_run = l_run * alpha + psum;

@@ -17,69 +17,16 @@
 // k-major -- a second DMA of the tile lays it out as 512-byte subtiles [8 rows][32 d] and ds_read_b64_tr_b16 gathers the fragments
 // (gemm_split.hip's k-major operands; round 4: the three planes_transpose launches per call and their scratch are gone).  Two
 // stages, one barrier per tile (explicit vmcnt(0) before it on every path).
-#include "common.h"
+#include "split_frag.h"
 #include "../../include/dupl_hip.h"
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-constexpr float LO_INV = 1.f / DUPL_LO_SCALE;
 constexpr int HD = 64, TT = 32;             // rows (keys or queries) per tile
 constexpr int PL = 4096;                    // bytes of one tile plane (row-major 32 x 128 B, or k-major: 8 subtiles of 512 B)
 constexpr int MAXN = 2048;                  // lse / delta of one (b, h) are kept in LDS by the key-owner kernels
 
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
-
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-
-__device__ __forceinline__ void xcd_remap3(int remap, int& bx, int& by, int& bz) {
-    bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
-    if (!remap) return;
-    const int gx = gridDim.x, gy = gridDim.y;
-    const int total = gx * gy * gridDim.z;
-    const int L = bx + gx * (by + gy * bz);
-    const int q = total >> 3, r = total & 7;
-    const int xcd = L & 7, idx = L >> 3;
-    const int w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    bx = w % gx;
-    by = (w / gx) % gy;
-    bz = w / (gx * gy);
-}
-
-__device__ __forceinline__ void dma16(const char* src, char* dst) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                     (__attribute__((address_space(3))) void*)dst, 16, 0, 0);
-}
-
-// MFMA row i <- tile row pi(i): 4-row groups 1 and 2 of every 16 swapped (see attn_split.hip)
-__device__ __forceinline__ int pi_row(int r) {
-    const int g = (r >> 2) & 3;
-    return (r & ~12) | ((g == 1 ? 2 : (g == 2 ? 1 : g)) << 2);
-}
-
-// k-major image of a [32 rows][64 d] tile plane: subtile (2 sg + jj) * 2 + dblk = [8 rows][32 d] halfs, holding rows
-// 16 sg + 4 jj + {0..3, 8..11} -- what one ds_read_b64_tr_b16 of row step sg, half jj gathers.  DMA piece w (1 KB, wave w) = row
-// group w, both d blocks: lane -> subtile row (lane >> 2) & 7, 16-byte chunk lane & 3 of d block lane >> 5.
-__device__ __forceinline__ int km_piece_row(int wave, int lane) {
-    const int srow = (lane >> 2) & 7;
-    return (wave >> 1) * 16 + (srow >> 2) * 8 + (wave & 1) * 4 + (srow & 3);
-}
-__device__ __forceinline__ int km_piece_col_bytes(int lane) { return ((lane >> 5) * 32 + (lane & 3) * 8) * 2; }
-// per-lane byte offset of the transposing reads inside a plane image (lane (g = lane >> 4, q = lane & 15): subtile row
-// (g >> 1) * 4 + (q >> 2), d 16 (g & 1) + 4 (q & 3) .. + 3)
-__device__ __forceinline__ int km_read_lane_off(int lane) {
-    const int g = lane >> 4, q = lane & 15;
-    return ((g >> 1) * 4 + (q >> 2)) * 64 + (16 * (g & 1) + 4 * (q & 3)) * 2;
-}
-// The reads are inline asm: behind an LDS-DMA hipcc waits vmcnt(0) before every ds_read_b64_tr_b16 builtin (gemm_split.hip), which
-// would drain the prefetch of the next tile; the consumer waits lgkmcnt(0) itself.
-template <int OFF>
-__device__ __forceinline__ h4 km_tr_read(const unsigned addr) {
-    h4 v;
-    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
-    return v;
-}
+// Row permutation pi, row-major and k-major piece plans, transposing reads, DMA and the packed hi / lo split: split_frag.h
 // all 16 fragments halves of one tile: [(sg * 2 + d) * 2 + plane][half]
 __device__ __forceinline__ void km_read_tile(const unsigned base_hi, h4 (&f)[8][2]) {
 #define KM_RD(SG, DD, PLN, JJ) f[((SG) * 2 + (DD)) * 2 + (PLN)][JJ] = km_tr_read<(PLN) * PL + (((SG) * 2 + (JJ)) * 2 + (DD)) * 512>(base_hi)
@@ -89,8 +36,7 @@ __device__ __forceinline__ void km_read_tile(const unsigned base_hi, h4 (&f)[8][
     KM_RD(1, 1, 0, 0); KM_RD(1, 1, 0, 1); KM_RD(1, 1, 1, 0); KM_RD(1, 1, 1, 1);
 #undef KM_RD
 }
-// the wait of the consumer: lgkmcnt(0), with every fragment as an in / out operand -- nothing that uses them (an MFMA is no memory
-// operation: a "memory" clobber alone does not hold it back) can be scheduled above it
+// the wait of the consumer: lgkmcnt(0), with every fragment as an in / out operand (split_frag.h, km_tr_read)
 __device__ __forceinline__ void km_wait(h4 (&f)[8][2]) {
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(f[0][0]), "+v"(f[0][1]), "+v"(f[1][0]), "+v"(f[1][1]), "+v"(f[2][0]), "+v"(f[2][1]), "+v"(f[3][0]), "+v"(f[3][1]),
@@ -101,22 +47,42 @@ __device__ __forceinline__ void km_wait(h4 (&f)[8][2]) {
 }
 __device__ __forceinline__ h8 h8of(const h4 lo, const h4 hi) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); }
 
-// hi / lo planes of 16 accumulator values, two at a time: one packed convert, one packed multiply, one FMA per element --
-// lo = f16(fma(f32(hi), -2048, 2048 x)) is the same value as f16((x - hi) * 2048) (every step before the final rounding is
-// exact), and hi is read back from the register that becomes the operand, so the two planes cannot disagree (cf. split_f32)
+// hi / lo planes of 16 accumulator values, two at a time
 __device__ __forceinline__ void split_regs(const f32x16& v, h8 (&hi)[2], h8 (&lo)[2]) {
-    typedef _Float16 h2v __attribute__((ext_vector_type(2)));
-    typedef float f2v __attribute__((ext_vector_type(2)));
 #pragma unroll
-    for (int e = 0; e < 16; e += 2) {
-        const f2v x2 = {v[e], v[e + 1]};
-        const h2v hh = __builtin_convertvector(x2, h2v);
-        const f2v q2 = x2 * f2v{DUPL_LO_SCALE, DUPL_LO_SCALE};
-        hi[e >> 3][e & 7] = hh[0];
-        hi[e >> 3][(e & 7) + 1] = hh[1];
-        lo[e >> 3][e & 7] = (_Float16)__builtin_fmaf((float)hh[0], -DUPL_LO_SCALE, q2[0]);
-        lo[e >> 3][(e & 7) + 1] = (_Float16)__builtin_fmaf((float)hh[1], -DUPL_LO_SCALE, q2[1]);
+    for (int e = 0; e < 16; e += 2) split_pair(f32x2{v[e], v[e + 1]}, hi[e >> 3], lo[e >> 3], e & 7);
+}
+
+// the last product of a tile, over its k-major fragments f: g^T += X^T w (X = K, dO or Q; w = dS^T, P or dS as planes wh / wl)
+__device__ __forceinline__ void last_product(const h4 (&f)[8][2], const h8 (&wh)[2], const h8 (&wl)[2], f32x16 (&gM)[2], f32x16 (&gX)[2]) {
+#pragma unroll
+    for (int sg = 0; sg < 2; ++sg) {
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            const h8 th = h8of(f[(sg * 2 + d) * 2][0], f[(sg * 2 + d) * 2][1]);
+            const h8 tl = h8of(f[(sg * 2 + d) * 2 + 1][0], f[(sg * 2 + d) * 2 + 1][1]);
+            gM[d] = MFMA16(th, wh[sg], gM[d]);
+            gX[d] = MFMA16(th, wl[sg], gX[d]);
+            gX[d] = MFMA16(tl, wh[sg], gX[d]);
+        }
     }
+}
+
+// gradient epilogue: (main + cross / 2048) * f -> the 64 floats of this lane's row at op (lane half hf owns 4 of every 8), and
+// their running |max|
+__device__ __forceinline__ void store_grad(float* op, const f32x16 (&gM)[2], const f32x16 (&gX)[2], const float f, const int hf, float& amx) {
+#pragma unroll
+    for (int d = 0; d < 2; ++d)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            float4 v;
+            v.x = (gM[d][4 * g + 0] + gX[d][4 * g + 0] * LO_INV) * f;
+            v.y = (gM[d][4 * g + 1] + gX[d][4 * g + 1] * LO_INV) * f;
+            v.z = (gM[d][4 * g + 2] + gX[d][4 * g + 2] * LO_INV) * f;
+            v.w = (gM[d][4 * g + 3] + gX[d][4 * g + 3] * LO_INV) * f;
+            amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
+            *reinterpret_cast<float4*>(op + d * 32 + 8 * g + 4 * hf) = v;
+        }
 }
 
 // delta[b][h][q] = sum_d dO[q][d] * O[q][d]   (fp32 operands)
@@ -171,17 +137,17 @@ __device__ __forceinline__ void attn_bwd16_dq_body(char* __restrict__ smem, cons
         const size_t oo = ((size_t)b * N + rr) * D + h * HD + 8 * hf;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            qh[s] = *reinterpret_cast<const h8*>(qkv_hi + qo + 16 * s);
-            ql[s] = *reinterpret_cast<const h8*>(qkv_lo + qo + 16 * s);
-            oh[s] = *reinterpret_cast<const h8*>(do_hi + oo + 16 * s);
-            ol[s] = *reinterpret_cast<const h8*>(do_lo + oo + 16 * s);
+            qh[s] = load_bfrag(qkv_hi + qo, s);
+            ql[s] = load_bfrag(qkv_lo + qo, s);
+            oh[s] = load_bfrag(do_hi + oo, s);
+            ol[s] = load_bfrag(do_lo + oo, s);
         }
     }
     const float my_lse = qv ? lse[((size_t)b * H + h) * N + qrow] : 0.f;
     const float my_delta = qv ? delta[((size_t)b * H + h) * N + qrow] * s_do : 0.f;
 
     // DMA plan: wave w fetches piece w of every plane
-    const int rrow = 8 * wave + (lane >> 3), rch = ((lane & 7) ^ ((rrow >> 1) & 7)) * 16;         // row-major pieces
+    const int rrow = 8 * wave + (lane >> 3), rch = rm_piece_col_bytes(lane, rrow);       // row-major pieces (split_frag.h)
     const int trow = km_piece_row(wave, lane), tcb = km_piece_col_bytes(lane);                    // k-major pieces
     const char* k_hi = reinterpret_cast<const char*>(qkv_hi + (size_t)b * N * ld + D + h * HD);
     const char* k_lo = reinterpret_cast<const char*>(qkv_lo + (size_t)b * N * ld + D + h * HD);
@@ -247,34 +213,13 @@ __device__ __forceinline__ void attn_bwd16_dq_body(char* __restrict__ smem, cons
         h8 dh[2], dl[2];
         split_regs(ds, dh, dl);
         km_wait(kf);
-#pragma unroll
-        for (int sg = 0; sg < 2; ++sg) {
-#pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                const h8 th = h8of(kf[(sg * 2 + d) * 2][0], kf[(sg * 2 + d) * 2][1]);
-                const h8 tl = h8of(kf[(sg * 2 + d) * 2 + 1][0], kf[(sg * 2 + d) * 2 + 1][1]);
-                dqM[d] = MFMA16(th, dh[sg], dqM[d]);
-                dqX[d] = MFMA16(th, dl[sg], dqX[d]);
-                dqX[d] = MFMA16(tl, dh[sg], dqX[d]);
-            }
-        }
+        last_product(kf, dh, dl, dqM, dqX);
     }
     float amx = 0.f;
     if (wave_active && qv) {
         const float f = scale * inv_s;
         float* op = dqkv + ((size_t)b * N + qrow) * ld + h * HD;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float4 v;
-                v.x = (dqM[d][4 * g + 0] + dqX[d][4 * g + 0] * LO_INV) * f;
-                v.y = (dqM[d][4 * g + 1] + dqX[d][4 * g + 1] * LO_INV) * f;
-                v.z = (dqM[d][4 * g + 2] + dqX[d][4 * g + 2] * LO_INV) * f;
-                v.w = (dqM[d][4 * g + 3] + dqX[d][4 * g + 3] * LO_INV) * f;
-                amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-                *reinterpret_cast<float4*>(op + d * 32 + 8 * g + 4 * hf) = v;
-            }
+        store_grad(op, dqM, dqX, f, hf, amx);
     }
     attn_bwd_amax_flush(amax_out, amx);
 }
@@ -312,16 +257,16 @@ __device__ __forceinline__ void attn_bwd16_dkv_body(char* __restrict__ smem, con
         const size_t ko = ((size_t)b * N + min(krow, N - 1)) * ld + D + h * HD + 8 * hf;
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-            kh[s] = *reinterpret_cast<const h8*>(qkv_hi + ko + 16 * s);
-            kl[s] = *reinterpret_cast<const h8*>(qkv_lo + ko + 16 * s);
+            kh[s] = load_bfrag(qkv_hi + ko, s);
+            kl[s] = load_bfrag(qkv_lo + ko, s);
             if (MODE == 1) {
-                vh[s] = *reinterpret_cast<const h8*>(qkv_hi + ko + D + 16 * s);
-                vl[s] = *reinterpret_cast<const h8*>(qkv_lo + ko + D + 16 * s);
+                vh[s] = load_bfrag(qkv_hi + ko + D, s);
+                vl[s] = load_bfrag(qkv_lo + ko + D, s);
             }
         }
     }
 
-    const int rrow = 8 * wave + (lane >> 3), rch = ((lane & 7) ^ ((rrow >> 1) & 7)) * 16;
+    const int rrow = 8 * wave + (lane >> 3), rch = rm_piece_col_bytes(lane, rrow);
     const int trow = km_piece_row(wave, lane), tcb = km_piece_col_bytes(lane);
     const char* q_hi = reinterpret_cast<const char*>(qkv_hi + (size_t)b * N * ld + h * HD);
     const char* q_lo = reinterpret_cast<const char*>(qkv_lo + (size_t)b * N * ld + h * HD);
@@ -401,34 +346,13 @@ __device__ __forceinline__ void attn_bwd16_dkv_body(char* __restrict__ smem, con
         h8 wh[2], wl[2];
         split_regs(w, wh, wl);
         km_wait(xf);
-#pragma unroll
-        for (int sg = 0; sg < 2; ++sg) {
-#pragma unroll
-            for (int d = 0; d < 2; ++d) {
-                const h8 th = h8of(xf[(sg * 2 + d) * 2][0], xf[(sg * 2 + d) * 2][1]);
-                const h8 tl = h8of(xf[(sg * 2 + d) * 2 + 1][0], xf[(sg * 2 + d) * 2 + 1][1]);
-                gM[d] = MFMA16(th, wh[sg], gM[d]);           // dv^T += dO^T P   /   dk^T += Q^T dS
-                gX[d] = MFMA16(th, wl[sg], gX[d]);
-                gX[d] = MFMA16(tl, wh[sg], gX[d]);
-            }
-        }
+        last_product(xf, wh, wl, gM, gX);           // dv^T += dO^T P   /   dk^T += Q^T dS
     }
     float amx = 0.f;
     if (wave_active && kv) {
         const float f = MODE == 0 ? inv_s : scale * inv_s;
         float* op = dqkv + ((size_t)b * N + krow) * ld + (MODE == 0 ? 2 * D : D) + h * HD;
-#pragma unroll
-        for (int d = 0; d < 2; ++d)
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                float4 v;
-                v.x = (gM[d][4 * g + 0] + gX[d][4 * g + 0] * LO_INV) * f;
-                v.y = (gM[d][4 * g + 1] + gX[d][4 * g + 1] * LO_INV) * f;
-                v.z = (gM[d][4 * g + 2] + gX[d][4 * g + 2] * LO_INV) * f;
-                v.w = (gM[d][4 * g + 3] + gX[d][4 * g + 3] * LO_INV) * f;
-                amx = fmaxf(fmaxf(amx, fmaxf(fabsf(v.x), fabsf(v.y))), fmaxf(fabsf(v.z), fabsf(v.w)));
-                *reinterpret_cast<float4*>(op + d * 32 + 8 * g + 4 * hf) = v;
-            }
+        store_grad(op, gM, gX, f, hf, amx);
     }
     attn_bwd_amax_flush(amax_out, amx);
 }
@@ -450,12 +374,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd16_all_kernel(const __half* __
     const int G = gx * H * B;
     const int role = __builtin_amdgcn_readfirstlane((int)blockIdx.x / G);     // 0: dk, 1: dq, 2: dv
     const int L = (int)blockIdx.x - role * G;
-    int w = L;
-    if (remap) {               // whole heads per XCD inside each role (xcd_remap3 on the role's own index)
-        const int q = G >> 3, r = G & 7;
-        const int xcd = L & 7, idx = L >> 3;
-        w = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int w = remap ? xcd_band(L, G) : L;      // whole heads per XCD inside each role
     const int bx = w % gx, h = (w / gx) % H, b = w / (gx * H);
     if (role == 0) attn_bwd16_dkv_body<1>(smem, bx, h, b, qkv_hi, qkv_lo, do_hi, do_lo, lse, delta, slot, dqkv, amax_out, N, H, scale);
     else if (role == 1) attn_bwd16_dq_body(smem, bx, h, b, qkv_hi, qkv_lo, do_hi, do_lo, lse, delta, slot, dqkv, amax_out, N, H, scale);

@@ -18,8 +18,7 @@
 // lane group hit 64 distinct banks (SQ_LDS_BANK_CONFLICT = 0).  Two LDS stages (64 KB, 2 blocks / CU), one barrier per
 // k-tile: the DMA of tile t+1 runs under the MFMAs of tile t.  Accumulating GEMMs (weight gradients) split K over
 // gridDim.y and add with fp32 atomics.
-#include "common.h"
-#include <type_traits>
+#include "split_frag.h"
 #include "../../include/dupl_hip.h"
 
 #ifndef G16_ABL
@@ -28,10 +27,7 @@
 
 namespace {
 
-typedef _Float16 h8 __attribute__((ext_vector_type(8)));
-
 constexpr int TBK = 32;
-constexpr float LO_INV = 1.f / DUPL_LO_SCALE;
 
 template <bool F1>
 __global__ __launch_bounds__(256) void split_kernel(const float* __restrict__ x, __half* __restrict__ hi, __half* __restrict__ lo,
@@ -740,14 +736,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, MINB) void gemm_f16x3_kernel(const 
 // s_waitcnt immediate (gfx9 encoding): lgkmcnt(0), expcnt untouched, vmcnt(n)
 #define WAIT_LGKM0_VM(n) ((((n) & 15) | (((n) >> 4) << 14)) | (7 << 4))
 
-template <int N, int I = 0, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<N, I + 1>(f);
-    }
-}
-
 // issue-order hints (hipcc keeps ds_read / MFMA / DMA clusters apart otherwise): NMF MFMAs spread over NR fragment reads
 // (phase A) or over NR reads + ND DMA pieces (phase B: reads and DMA alternate while both remain)
 template <int NMF, int NR, int R = 0>
@@ -1365,7 +1353,6 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(c
 // SK: stream-K over (tile, k-step) as in gemm_f16x3_pring_kernel, pieces meet in fp32 atomics (ACC 1); ACC 2: C += tile by the one
 // block that owns the tile (deterministic mode); ACC 0: the full epilogue (bias / activation / aux / planes / amax).
 typedef short s4v __attribute__((ext_vector_type(4)));
-typedef _Float16 h4 __attribute__((ext_vector_type(4)));
 // phase B of the k-major kernel: NR read instructions and ND DMA pieces alternate, the rarer kind spread over the other
 constexpr bool slot_is_read(int S, int NR, int ND) {
     int rd = 0, dd = 0;
@@ -1474,11 +1461,9 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
     const int sw = (l31 >> 2) & 3;
     const int a_row = (wm * (32 * WM) + l31) * 64, b_row = 2 * PA * 1024 + (wn * (32 * WN) + l31) * 64;
     const int c0 = ((0 | hf) ^ sw) * 16, c1 = ((2 | hf) ^ sw) * 16;
-    // k-major: lane (g = lane >> 4, q = lane & 15) of the read (k-step ks, half jj) takes subtile row (g >> 1) * 4 + (q >> 2), rows
-    // 16 (g & 1) + 4 (q & 3) .. + 3 of the 32-row block wm WM + i, in subtile (ks * 2 + jj) * (BM / 32) + block: one base per lane,
-    // everything else is an immediate offset
-    const int g4 = lane >> 4, q15 = lane & 15;
-    const int kml = ((g4 >> 1) * 4 + (q15 >> 2)) * 64 + (16 * (g4 & 1) + 4 * (q15 & 3)) * 2;
+    // k-major: the read (k-step ks, half jj) of the 32-row block wm WM + i takes subtile (ks * 2 + jj) * (BM / 32) + block at the lane
+    // offset of split_frag.h: one base per lane, everything else is an immediate offset
+    const int kml = km_read_lane_off(lane);
     const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);      // LDS byte address of stage 0
     const unsigned akm0 = lds0 + kml + wm * WM * 512, bkm0 = lds0 + 2 * PA * 1024 + kml + wn * WN * 512;
 
@@ -1486,17 +1471,9 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
     f32x16 accX_unused[1][1];
     // fragments as 4-half halves: [2 t], [2 t + 1] = k 0..3 / 4..7 of fragment t; t < W: hi plane, t >= W: lo plane
     h4 f0a[4 * WM], f0b[4 * WN], f1a[4 * WM], f1b[4 * WN];
-    // The transposing reads are INLINE ASM: behind a direct-to-LDS DMA hipcc puts `s_waitcnt vmcnt(0)` in front of every
-    // ds_read_b64_tr_b16 it issues itself (the builtin carries no alias information, so every LDS-DMA in flight "may" feed it) --
-    // that drains the two-tiles-ahead DMA ring once per read (measured: 87 instead of 165 TF/s-eq).  The ring's own protocol
-    // (counted vmcnt + barrier before a stage is read, lgkmcnt(0) + barrier before it is overwritten) already orders them; what the
-    // compiler no longer does for these reads is wait for their RESULTS, so every consumer phase starts with an explicit
-    // lgkmcnt(0) (LDS operations return in order: waits the compiler computes for its own reads can only become stricter).
-    auto tr_read = [](const unsigned addr, auto offc) __attribute__((always_inline)) {
-        h4 v;
-        asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(v) : "v"(addr), "n"(decltype(offc)::value) : "memory");
-        return v;
-    };
+    // The transposing reads are km_tr_read (inline asm, split_frag.h): every consumer phase starts with an explicit lgkmcnt(0).
+    // They go through this adapter (offset as a value): called directly, two register moves of one instantiation change places.
+    auto tr_off = [](const unsigned addr, auto offc) __attribute__((always_inline)) { return km_tr_read<decltype(offc)::value>(addr); };
     // one LDS read instruction: RI-th of the A / B operand (KS = k-step inside the tile); st = stage pointer, so = its byte offset
     auto read_a = [&](auto ric, auto ksc, const char* st, const unsigned so, h4(&fa)[4 * WM]) __attribute__((always_inline)) {
         constexpr int RI = decltype(ric)::value, KS = decltype(ksc)::value;
@@ -1507,7 +1484,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
             fa[2 * t + 1] = __builtin_shufflevector(v, v, 4, 5, 6, 7);
         } else {
             constexpr int t = RI / 2, half = RI % 2;
-            fa[2 * t + half] = tr_read(akm0 + so, std::integral_constant<int, (t < WM ? 0 : PA * 1024) + ((KS * 2 + half) * (BM / 32) + (t % WM)) * 512>{});
+            fa[2 * t + half] = tr_off(akm0 + so, std::integral_constant<int, (t < WM ? 0 : PA * 1024) + ((KS * 2 + half) * (BM / 32) + (t % WM)) * 512>{});
         }
     };
     auto read_b = [&](auto ric, auto ksc, const char* st, const unsigned so, h4(&fb)[4 * WN]) __attribute__((always_inline)) {
@@ -1519,7 +1496,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
             fb[2 * t + 1] = __builtin_shufflevector(v, v, 4, 5, 6, 7);
         } else {
             constexpr int t = RI / 2, half = RI % 2;
-            fb[2 * t + half] = tr_read(bkm0 + so, std::integral_constant<int, (t < WN ? 0 : PB * 1024) + ((KS * 2 + half) * (BN / 32) + (t % WN)) * 512>{});
+            fb[2 * t + half] = tr_off(bkm0 + so, std::integral_constant<int, (t < WN ? 0 : PB * 1024) + ((KS * 2 + half) * (BN / 32) + (t % WN)) * 512>{});
         }
     };
     // R-th read instruction of a k-step (A's first, then B's)

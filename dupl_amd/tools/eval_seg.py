@@ -16,6 +16,7 @@ from collections import OrderedDict
 import torch
 
 from .. import ops
+from ..model.backbone import FAMILY
 from ..utils import evaluate
 from ..utils.pyutils import format_tabs
 
@@ -24,6 +25,17 @@ def load_checkpoint(model, path_or_state):
     """tools/eval_seg_voc.py:173-178: strip the DDP `module.` prefix and load strictly."""
     sd = torch.load(path_or_state, map_location="cpu") if isinstance(path_or_state, str) else path_or_state
     new = OrderedDict((k.replace("module.", ""), v) for k, v in sd.items())
+    # a checkpoint of another --backbone: say so in one line (strict loading would list every tensor of every block)
+    want = model.state_dict()
+    for k, v in new.items():
+        if k.endswith("encoder.cls_token") and k in want and v.shape[-1] != want[k].shape[-1]:
+            raise ValueError(f"checkpoint is of another backbone: expected width {want[k].shape[-1]} "
+                             f"(--backbone {getattr(model, '_ctor', ('?',))[0]}), found width {v.shape[-1]} ({k})")
+    depth = {m: 1 + max((int(k.split(".")[3]) for k in d if k.startswith("branch1.encoder.blocks.")), default=-1)
+             for m, d in (("expected", want), ("found", new))}
+    if depth["expected"] != depth["found"] and depth["found"] > 0:
+        raise ValueError(f"checkpoint is of another backbone: expected depth {depth['expected']} "
+                         f"(--backbone {getattr(model, '_ctor', ('?',))[0]}), found depth {depth['found']}")
     model.load_state_dict(new, strict=True)
     return model
 
@@ -172,7 +184,8 @@ def build_parser(dataset: str = "voc"):
     p.add_argument("--infer_set", default="val" if voc_ else "val_part", type=str)
     p.add_argument("--pooling", default="gmp", type=str)
     p.add_argument("--model_path", default="your_model_dir/checkpoints.pth", type=str)
-    p.add_argument("--backbone", default="deit_base_patch16_224" if voc_ else "vit_base_patch16_224", type=str)
+    p.add_argument("--backbone", default="deit_base_patch16_224" if voc_ else "vit_base_patch16_224", type=str,
+                   help="the checkpoint's backbone: " + " | ".join(FAMILY))
     if voc_:
         p.add_argument("--data_folder", default="your_voc_dir", type=str, help="dataset folder")
     else:

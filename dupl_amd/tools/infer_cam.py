@@ -19,6 +19,7 @@ from .. import ops
 from ..utils import cam_helper, evaluate
 from ..utils.pyutils import format_tabs
 from .eval_seg import load_checkpoint
+from ..model.backbone import FAMILY
 
 
 def build_parser():
@@ -27,7 +28,7 @@ def build_parser():
     p = argparse.ArgumentParser()
     p.add_argument("--bkg_thre", default=0.5, type=float, help="background threshold of the score table and the label PNGs")
     p.add_argument("--model_path", default="your_model_path/checkpoint.pth", type=str, help="model_path")
-    p.add_argument("--backbone", default="vit_base_patch16_224", type=str, help="vit_base_patch16_224")
+    p.add_argument("--backbone", default="vit_base_patch16_224", type=str, help="the checkpoint's backbone: " + " | ".join(FAMILY))
     p.add_argument("--pooling", default="gmp", type=str, help="pooling choice for patch tokens")
     p.add_argument("--data_folder", default="your_voc_dir", type=str, help="dataset folder")
     p.add_argument("--num_classes", default=21, type=int, help="number of classes")

@@ -18,6 +18,7 @@ import torch.distributed as dist
 
 
 def build_parser(dataset: str) -> argparse.ArgumentParser:
+    from .model.backbone import FAMILY
     voc = dataset == "voc"
     p = argparse.ArgumentParser()
     p.add_argument("--comment", default="_train_voc" if voc else "_train_coco", type=str, help="comment")
@@ -34,9 +35,10 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--train_set", default="train_aug" if voc else "train", type=str)
     p.add_argument("--val_set", default="val" if voc else "val_part", type=str)
     p.add_argument("--scales", default=(0.5, 2), help="random rescale in training")
-    p.add_argument("--backbone", default="deit_base_patch16_224", type=str, help="backbone")
+    p.add_argument("--backbone", default="deit_base_patch16_224", type=str,
+                   help="backbone: " + " | ".join(FAMILY))
     p.add_argument("--pooling", default="gmp", type=str)
-    p.add_argument("--pretrained", default=False, help="path to a local ImageNet state_dict (no network here)")
+    p.add_argument("--pretrained", default=False, help="path to the local ImageNet state_dict of --backbone (no network here)")
     if voc:
         p.add_argument("--aux_layer", default=-3, type=int, help="aux_layer")
     p.add_argument("--samples_per_gpu", default=2 if voc else 1, type=int, help="samples_per_gpu")
@@ -78,7 +80,7 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--single_stream", action="store_true")
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible steps (dupl_amd.set_deterministic): what cudnn.deterministic = True asks for in "
-                        "the reference's setup_seed (train_final_voc.py:95-102); costs ~20 % throughput")
+                        "the reference's setup_seed (train_final_voc.py:95-102); costs ~20 %% throughput")
     return p
 
 

@@ -1,7 +1,11 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval]
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] | backbone
 `crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81.
-`cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces."""
+`cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces.
+`backbone` (only when named; then nothing else runs) times one phase-B training step at VOC 448^2, 4 images, two student streams
+for every registered --backbone, or for the names that follow it: bench.py's own workload and timed region (bench.Workload.measure:
+warm-up steps, then K steps between synchronisations), so the deit_base_patch16_224 row is bench.py's figure.
+    python tools/op_bench.py backbone [name ...] [steps=20] [warmup=5]"""
 import gc
 import sys
 
@@ -93,7 +97,40 @@ def cam_eval_bench(dev, g):
                   f"composed {t_c:.1f} us ({t_c / t_f:.1f}x ops.cam_eval); with the global-atomics histogram {t_g:.1f} us")
 
 
+def backbone_bench(argv):
+    """ms / step and img / s of one phase-B step (VOC, 448^2, 4 images on one GPU, two streams) per backbone."""
+    import os
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    from dupl_amd.model.backbone import FAMILY
+    opts = dict(a.split("=", 1) for a in argv if "=" in a)
+    names = [a for a in argv if a in FAMILY] or list(FAMILY)
+    unknown = [a for a in argv if a != "backbone" and "=" not in a and a not in FAMILY]
+    assert not unknown, f"not a registered backbone: {unknown}; registered: {FAMILY}"
+    steps, warmup = int(opts.get("steps", 20)), int(opts.get("warmup", 5))
+    sys.argv = [sys.argv[0], "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup)]
+    import bench
+    args = bench.parse()
+    rows = []
+    for name in names:
+        wl = bench.Workload(args, 1, 0, 0, "voc", 4, name, bench.DEFAULT_N_ITER["voc"])
+        assert wl.phase == "B", wl.phase
+        res = wl.measure(name)
+        cfg = wl.model.branch1._cfg
+        g = wl.model.flat_storage.guard.summary()
+        rows.append((name, cfg, res["ms"], res["value"], g))
+        print(f"backbone {name}: D {cfg.embed_dim} depth {cfg.depth} heads {cfg.num_heads} grid {cfg.grid}: {res['ms']:.2f} ms / step, "
+              f"{res['value']:.2f} img / s (loss {res['loss']:.4f}; sites on f32 {g['sites_on_f32']}, on format 0 {g['sites_on_fmt0']})", flush=True)
+        del wl, res
+        gc.collect()
+        torch.cuda.empty_cache()
+    print(f"\n| backbone | embed dim | depth | heads | pos-embed grid | ms / step | img / s |\n|---|---|---|---|---|---|---|")
+    for name, cfg, ms, v, _ in rows:
+        print(f"| `{name}` | {cfg.embed_dim} | {cfg.depth} | {cfg.num_heads} | {cfg.grid} x {cfg.grid} | {ms:.2f} | {v:.2f} |")
+
+
 def main():
+    if "backbone" in sys.argv[1:]:
+        return backbone_bench(sys.argv[1:])
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)

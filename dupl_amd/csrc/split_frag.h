@@ -13,6 +13,7 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr float LO_INV = 1.f / DUPL_LO_SCALE;
 
 #define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_32x32x16_f16((a), (b), (c), 0, 0, 0)
+#define MFMA_16x16x32(a, b, c) __builtin_amdgcn_mfma_f32_16x16x32_f16((a), (b), (c), 0, 0, 0)
 
 template <int N, int I = 0, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -60,12 +61,26 @@ __device__ __forceinline__ void dma16(const char* src, char* dst) {
 // ds_read_b128).  The row stays written out at its three call sites: as a helper it changes the code of both attention kernels.
 __device__ __forceinline__ int rm_piece_col_bytes(int lane, int row) { return ((lane & 7) ^ ((row >> 1) & 7)) * 16; }
 
+// The same planes for the A operand of v_mfma_f32_16x16x32_f16 fed in the order pi16 (below): the 16 lanes of one k group read
+// rows 8 (c >> 2) + 4 j + (c & 3) (c = lane & 15) at source chunk 4 kstep + (lane >> 4).  Rows 16 apart share (row >> 1) & 7, so
+// the swizzle above is 2-way there; this one takes row bits 1, 3 and 4 -- the three bits of c besides row & 1 that vary in a read
+// -- and is conflict-free in the four 16-lane groups of ds_read_b128 ({0-3, 12-15, 20-27}, ...: a group mixes two k groups g,
+// g ^ 1 by (c >> 2) in {1, 2}, which XORs bit 0 of the chunk with c2 ^ c3 -- still one-to-one in (c1, c2, c3)).
+__device__ __forceinline__ int rm16_swizzle(int row) { return ((row >> 1) & 1) | (((row >> 3) & 3) << 1); }
+__device__ __forceinline__ int rm16_piece_col_bytes(int lane, int row) { return ((lane & 7) ^ rm16_swizzle(row)) * 16; }
+
 // MFMA row i <- tile row pi(i): 4-row groups 1 and 2 of every 16 swapped, so that the accumulator registers 8 s .. 8 s + 7 of a lane
 // are tile rows 16 s + 8 hf + 0..7 -- the B fragment of the next product, without any permute (attn_split.hip's formulation)
 __device__ __forceinline__ int pi_row(int r) {
     const int g = (r >> 2) & 3;
     return (r & ~12) | ((g == 1 ? 2 : (g == 2 ? 1 : g)) << 2);
 }
+
+// The same idea for a chain of two 16x16x32 products (attn_fwd16_m16_kernel).  Lane (c = lane & 15, g = lane >> 4) holds rows
+// 4 g .. 4 g + 3 of column c of a 16 x 16 result and needs k = 8 g .. 8 g + 7 of column c as the next B operand.  A 32-row group is
+// computed as two 16-row tiles T0, T1, and MFMA row r of tile Tj is fed with row pi16(r, j) = 8 (r >> 2) + 4 j + (r & 3) of the
+// group: the lane then holds rows 8 g .. 8 g + 3 in T0 and 8 g + 4 .. 8 g + 7 in T1 -- the fragment, without any permute.
+__device__ __forceinline__ int pi16_row(int r, int j) { return 8 * (r >> 2) + 4 * j + (r & 3); }
 
 // B-operand fragment s (of 4) of a row held in registers: lane half hf holds halfs 16 s + 8 hf .. + 7; p points at the row's half
 // 8 hf.  (One step at a time: a helper that loads the 4 steps of a plane reorders the callers' interleaved global loads.)
@@ -87,6 +102,17 @@ __device__ __forceinline__ int km_read_lane_off(int lane) {
     const int g = lane >> 4, q = lane & 15;
     return ((g >> 1) * 4 + (q >> 2)) * 64 + (16 * (g & 1) + 4 * (q & 3)) * 2;
 }
+// ---- the same for the 16x16x32 MFMA (A = [16 d][32 rows]: lane (d, g) needs rows 8 g .. 8 g + 7).  The image of a [64 rows][64 d]
+// tile plane is 16 subtiles of 512 bytes: subtile ((S * 2 + jj) * 4 + dt) = [16 rows][16 d] halfs, subtile row 4 g + i holding row
+// 32 S + 8 g + 4 jj + i, d 16 dt .. + 15 -- what one ds_read_b64_tr_b16 of row step S, half jj, d tile dt gathers, at lane * 8 bytes
+// (contiguous: conflict-free).  DMA piece p (1 KB, 8 per plane) = subtiles 2 p, 2 p + 1: lane -> subtile lane >> 5, subtile row
+// (lane >> 1) & 15, 16-byte half lane & 1 of the row's 32 bytes.
+__device__ __forceinline__ int km16_piece_row(int p, int lane) {
+    const int sr = (lane >> 1) & 15;
+    return (p >> 2) * 32 + (sr >> 2) * 8 + ((p >> 1) & 1) * 4 + (sr & 3);
+}
+__device__ __forceinline__ int km16_piece_col_bytes(int p, int lane) { return (16 * (2 * (p & 1) + (lane >> 5)) + 8 * (lane & 1)) * 2; }
+__device__ __forceinline__ int km16_read_lane_off(int lane) { return lane * 8; }
 // The transposing reads are INLINE ASM: behind a direct-to-LDS DMA hipcc puts `s_waitcnt vmcnt(0)` in front of every
 // ds_read_b64_tr_b16 it issues itself (the builtin carries no alias information, so every LDS-DMA in flight "may" feed it) -- that
 // drains the prefetch of the next tiles once per read (gemm_split.hip's ring: 87 instead of 165 TF/s-eq).  The kernels' own

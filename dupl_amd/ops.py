@@ -564,6 +564,11 @@ def attention_fwd(qkv: Tensor, B: int, N: int, H: int, hd: int, scale: float, ne
     return out, lse
 
 
+# the MFMA shape of the split attention forward (dupl_attention_fwd16_mfma): 0 = the library's choice, 32 = attn_fwd16_kernel
+# (32x32x16), 16 = attn_fwd16_m16_kernel (16x16x32)
+ATTN16_TUNING = {"mfma": int(_os.environ.get("DUPL_ATTN16_MFMA", "0"))}
+
+
 def attention_fwd16(qkv16, B: int, N: int, H: int, hd: int, scale: float, need_lse: bool = False,
                     out: Optional[Tensor] = None, out16=None, b_f32: int = 0):
     """Attention forward on the f16x3 split kernels (head dim 64).  qkv16: Split16 / Split16View [B*N, 3*H*hd] (planes of
@@ -576,9 +581,9 @@ def attention_fwd16(qkv16, B: int, N: int, H: int, hd: int, scale: float, need_l
     if out is not None:
         assert out.shape == (bf * N, H * hd) and out.is_contiguous()
     assert getattr(qkv16, "exp", 0) == 0, "the split attention reads format 0 planes"
-    L().dupl_attention_fwd16(qkv16.hi, qkv16.lo, _p(out), out16.hi if out16 is not None else None,
-                              out16.lo if out16 is not None else None, _p(lse), B, N, H, hd, float(scale), bf,
-                              out16.exp if out16 is not None else 0, _stream())
+    L().dupl_attention_fwd16_mfma(qkv16.hi, qkv16.lo, _p(out), out16.hi if out16 is not None else None,
+                                   out16.lo if out16 is not None else None, _p(lse), B, N, H, hd, float(scale), bf,
+                                   out16.exp if out16 is not None else 0, ATTN16_TUNING["mfma"], _stream())
     return lse
 
 
@@ -599,9 +604,9 @@ def attention_fwd16_segs(qkv16, segs, H: int, hd: int, scale: float, out16=None)
         lses.append(lse)
         arr[i].row0, arr[i].B, arr[i].N, arr[i].B_f32 = int(row0), int(B), int(N), int(b_f32)
         arr[i].out, arr[i].lse = _p(out), _p(lse)
-    L().dupl_attention_fwd16_segs(qkv16.hi, qkv16.lo, out16.hi if out16 is not None else None,
-                                   out16.lo if out16 is not None else None, ctypes.cast(arr, ctypes.c_void_p), len(segs), H, hd,
-                                   float(scale), out16.exp if out16 is not None else 0, _stream())
+    L().dupl_attention_fwd16_segs_mfma(qkv16.hi, qkv16.lo, out16.hi if out16 is not None else None,
+                                        out16.lo if out16 is not None else None, ctypes.cast(arr, ctypes.c_void_p), len(segs), H, hd,
+                                        float(scale), out16.exp if out16 is not None else 0, ATTN16_TUNING["mfma"], _stream())
     return lses
 
 

@@ -288,6 +288,18 @@ class FlatStorage:
         self._w16T[(student, key)] = (ver, T)
         return T
 
+    def w16T_tc(self, student: int, key: str, rows: int, cin: int):
+        """w16T of a 3x3 conv weight [rows, cin * 9] with the plane rows in (tap, c) order (ops.split_wT_tc): the data gradient
+        then comes out tap-major (dupl_col2im_dil3_tc).  Cached under its own key: the (c, tap) planes of the same weight are a
+        different matrix."""
+        ver = self._param_key()
+        hit = self._w16T.get((student, key, "tc"))
+        if hit is not None and hit[0] == ver:
+            return hit[1]
+        T = ops.split_wT_tc(self.view(student, key).view(rows, -1), cin)
+        self._w16T[(student, key, "tc")] = (ver, T)
+        return T
+
     def w16T_missing(self, student: int, keys_rows):
         """[(key, rows, fp32 view [rows, cols])] of the parameters whose transposed planes are stale: the caller splits them
         (together with other operands, ops.split_prepare_multi) and hands the planes back through w16T_put."""
@@ -599,6 +611,9 @@ class StudentParams:
 
     def w16T(self, key: str, rows: int):
         return self.store.w16T(self.student, key, rows)
+
+    def w16T_tc(self, key: str, rows: int, cin: int):
+        return self.store.w16T_tc(self.student, key, rows, cin)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -932,6 +947,14 @@ class HeadSaved:
     col7: Tensor = None
     h7: Tensor = None
     guard: dict = None         # f16x3 mode: the RangeGuard verdicts the decoder convs ran with
+    col6T16: object = None     # a conv that ran on planes (DECODER_PLANES): col^T planes [9 Cin, Mp] instead of the fp32 col
+    col7T16: object = None
+
+
+# The LargeFOV convs on operand planes (bit-equal to the fp32-col route, which DUPL_DECODER_PLANES=0 keeps reachable):
+# bit 0: im2col writes the forward GEMM's planes and the weight gradient's transposed planes directly (no fp32 col, no split passes);
+# bit 1: the data gradient is computed tap-major (W^T planes with rows in (tap, c) order) and gathered by dupl_col2im_dil3_tc.
+DECODER_PLANES = int(os.environ.get("DUPL_DECODER_PLANES", "3"))
 
 
 def _prefix_saved(sv: EncoderSaved, b: int, rows: int) -> EncoderSaved:
@@ -1020,29 +1043,34 @@ def network_forward(P: StudentParams, x: Tensor, save: bool, enc_cache=None):
     x4 = ops.tokens_to_nchw(tf, B, n, D, h, w, skip_cls=True)
     # LargeFOV on the patch tokens (token-major, cls row skipped through the image stride)
     dd, dil = cfg.decoder_dim, cfg.decoder_dilation
-    col6 = torch.empty((B * n, 9 * D), device=x.device, dtype=torch.float32)
-    ops.L().dupl_im2col_dil3(tf.data_ptr() + 4 * D, col6.data_ptr(), B, h, w, D, dil, D, (n + 1) * D, ops._stream())
     f16 = GEMM_MODE == "f16x3"        # the two 3x3 convs (K = 9 * 768 / 9 * 512) as split GEMMs; conv8 (N = classes) stays f32
     guard = None
     if f16:
         P.store.ensure_w16(P.student)
         guard = P.store.guard.sites(P.student)
-    if f16 and guard["conv6"]:
-        h6, _ = _lin16(P, ops.split16(col6), P.w16("decoder.conv6.weight", dd), relu=True)
-    else:
-        h6 = ops.linear(col6, P.w["decoder.conv6.weight"].view(dd, -1), relu=True)
-    col7 = torch.empty((B * n, 9 * dd), device=x.device, dtype=torch.float32)
-    ops.L().dupl_im2col_dil3(h6.data_ptr(), col7.data_ptr(), B, h, w, dd, dil, dd, n * dd, ops._stream())
-    if f16 and guard["conv7"]:
-        h7, _ = _lin16(P, ops.split16(col7), P.w16("decoder.conv7.weight", dd), relu=True)
-    else:
-        h7 = ops.linear(col7, P.w["decoder.conv7.weight"].view(dd, -1), relu=True)
+    Mp = (B * n + 31) // 32 * 32
+
+    def conv(site, src_ptr, Cin, ld, img_stride):
+        """One 3x3 dilated conv + ReLU; returns (h, fp32 col | None, col^T planes | None)."""
+        Wk = f"decoder.{site}.weight"
+        if f16 and guard[site] and (DECODER_PLANES & 1) and Cin % 8 == 0:
+            # on planes: im2col writes the GEMM's A planes and (for the backward's weight gradient) their transpose; no fp32 col
+            c16, cT16 = ops.im2col_dil3_planes(src_ptr, x.device, B, h, w, Cin, dil, ld, img_stride, want_T=save, rows_pad=Mp)
+            return _lin16(P, c16, P.w16(Wk, dd), relu=True)[0], None, cT16
+        col = torch.empty((B * n, 9 * Cin), device=x.device, dtype=torch.float32)
+        ops.L().dupl_im2col_dil3(src_ptr, col.data_ptr(), B, h, w, Cin, dil, ld, img_stride, ops._stream())
+        if f16 and guard[site]:
+            return _lin16(P, ops.split16(col), P.w16(Wk, dd), relu=True)[0], col, None
+        return ops.linear(col, P.w[Wk].view(dd, -1), relu=True), col, None      # the guard routed the site to exact f32
+
+    h6, col6, col6T = conv("conv6", tf.data_ptr() + 4 * D, D, D, (n + 1) * D)
+    h7, col7, col7T = conv("conv7", h6.data_ptr(), dd, dd, n * dd)
     seg_tok = ops.linear(h7, P.w["decoder.conv8.weight"].view(P.num_classes, dd))
     seg = ops.tokens_to_nchw(seg_tok, B, n, P.num_classes, h, w, skip_cls=False)
     sv = None
     if save:
         sv = HeadSaved(enc=enc, tf=tf, aux=aux, pooled=pooled, pooled_idx=pidx, pooled_aux=pooled_a, pooled_aux_idx=paidx,
-                       col6=col6, h6=h6, col7=col7, h7=h7, guard=guard)
+                       col6=col6, h6=h6, col7=col7, h7=h7, guard=guard, col6T16=col6T, col7T16=col7T)
     return (cls_x4, seg, x4, cls_aux), sv
 
 
@@ -1159,7 +1187,7 @@ def _linear_backward16_km(P: StudentParams, dy: Tensor, x16, name: str, dgelu_of
 
 
 def _linear_backward16(P: StudentParams, dy: Tensor, x: Tensor, name: str, dgelu_of: Optional[Tensor] = None,
-                       has_bias: bool = True, dx_feeds_split: bool = False, xT16=None) -> Tensor:
+                       has_bias: bool = True, dx_feeds_split: bool = False, xT16=None, wT16=None) -> Tensor:
     """The same on the f16x3 split GEMM (fp32-equivalent).  The gradient dy is scaled by a power of two from its own
     max-abs before it is split (its values are far below fp16's normal range); both GEMMs run as k-contiguous products
     through transposed operand planes:  dW += dy^T16 . (x^T16)^T,  dx = dy16 . (W^T16)^T  (csrc/split_prep.hip)."""
@@ -1175,7 +1203,9 @@ def _linear_backward16(P: StudentParams, dy: Tensor, x: Tensor, name: str, dgelu
     if has_bias and not fuse_bias:
         ops.colsum(dy, P.g[name + ".bias"], accumulate=True)
     # dx_feeds_split: dx is the next Linear's dy -> its max-abs comes out of this epilogue (ops.reserve_amax)
-    dx, _ = _lin16(P, dy16, P.w16T(name + ".weight", N), alpha=alpha, dgelu_of=dgelu_of, amax_for_next=dx_feeds_split)
+    # wT16: the caller's W^T planes (the decoder's tap-major ones, w16T_tc) in place of the cached (c, tap) ones
+    dx, _ = _lin16(P, dy16, wT16 if wT16 is not None else P.w16T(name + ".weight", N), alpha=alpha, dgelu_of=dgelu_of,
+                   amax_for_next=dx_feeds_split)
     return dx
 
 
@@ -1247,15 +1277,23 @@ def network_backward(P: StudentParams, sv: HeadSaved, dcls: Optional[Tensor], ds
         dh7 = ops.linear_dgrad(dseg_tok, W["decoder.conv8.weight"].view(NC, dd), relumask_of=sv.h7)
         f16 = GEMM_MODE == "f16x3"
         guard = (sv.guard or P.store.guard.sites(P.student)) if f16 else None
-        conv_bwd = _linear_backward16 if (f16 and guard["conv7"]) else _linear_backward32
-        dcol7 = conv_bwd(P, dh7, sv.col7, "decoder.conv7", has_bias=False)
+
+        def conv_bwd(site, dy, col, colT16, Cin, dx_ptr, ld, img_stride, accumulate, relu_of):
+            """dW += dy^T col and dx (+)= col2im(dy W) [relu_of > 0] of one 3x3 conv."""
+            name = f"decoder.{site}"
+            if not (f16 and guard[site]):
+                dcol, tc = _linear_backward32(P, dy, col, name, has_bias=False), False
+            else:
+                # tap-major data gradient: the same k-sums stored at column tap * Cin + c, which col2im reads in float4 runs
+                tc = bool(DECODER_PLANES & 2) and Cin % 4 == 0
+                dcol = _linear_backward16(P, dy, col, name, has_bias=False, xT16=colT16,
+                                          wT16=P.w16T_tc(name + ".weight", dd, Cin) if tc else None)
+            fn = ops.L().dupl_col2im_dil3_tc if tc else ops.L().dupl_col2im_dil3
+            fn(dcol.data_ptr(), dx_ptr, B, h, w, Cin, dil, ld, img_stride, accumulate, relu_of, ops._stream())
+
         dh6 = torch.empty((B * n, dd), device=dev, dtype=torch.float32)
-        ops.L().dupl_col2im_dil3(dcol7.data_ptr(), dh6.data_ptr(), B, h, w, dd, dil, dd, n * dd, 0, sv.h6.data_ptr(), ops._stream())
-        del dcol7
-        conv_bwd = _linear_backward16 if (f16 and guard["conv6"]) else _linear_backward32
-        dcol6 = conv_bwd(P, dh6, sv.col6, "decoder.conv6", has_bias=False)
-        ops.L().dupl_col2im_dil3(dcol6.data_ptr(), dtf.data_ptr() + 4 * D, B, h, w, D, dil, D, N * D, 1, None, ops._stream())
-        del dcol6
+        conv_bwd("conv7", dh7, sv.col7, sv.col7T16, dd, dh6.data_ptr(), dd, n * dd, 0, sv.h6.data_ptr())
+        conv_bwd("conv6", dh6, sv.col6, sv.col6T16, D, dtf.data_ptr() + 4 * D, D, N * D, 1, None)
         P.mark_grad(SEG_DECODER)
     if on_ready is not None:
         on_ready("heads")

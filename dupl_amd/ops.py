@@ -288,6 +288,32 @@ def split_prepare_multi(items):
     return out
 
 
+def im2col_dil3_planes(x_ptr: int, device, B: int, h: int, w: int, Cin: int, dil: int, ld: int, img_stride: int,
+                       want_rm: bool = True, want_T: bool = False, rows_pad: int = 0):
+    """3x3 dilated im2col of a token-major fp32 operand (raw pointer; row stride ld, image stride img_stride, both in floats)
+    straight into format 0 operand planes (csrc/conv.hip im2col_dil3_planes_kernel): row-major [B*h*w, 9*Cin] and / or transposed
+    [9*Cin, Mp] with zero rows up to Mp = rows_pad (default: B*h*w rounded up to 32) -- bit-equal to split16(col) and to
+    split_prepare(col, scaled=False, want_T=True, rows_pad=Mp) of the fp32 col, which never exists.  Returns (rm | None, T | None)."""
+    M = B * h * w
+    Mp = rows_pad if rows_pad else (M + 31) // 32 * 32
+    rm = split16_empty(M, 9 * Cin, device) if want_rm else None
+    T = split16_empty(9 * Cin, Mp, device) if want_T else None
+    L().dupl_im2col_dil3_planes(x_ptr, rm.hi if rm else None, rm.lo if rm else None, T.hi if T else None, T.lo if T else None,
+                                B, h, w, Cin, dil, ld, img_stride, Mp, _stream())
+    return rm, T
+
+
+def split_wT_tc(w: Tensor, Cin: int) -> Split16:
+    """Transposed format 0 planes [9*Cin, Cout] of a conv weight viewed as [Cout, 9*Cin] (column c*9 + tap), rows in (tap, c)
+    order: the B operand that makes the data gradient dy . W come out tap-major for dupl_col2im_dil3_tc."""
+    _chk(w)
+    Cout = w.shape[0]
+    assert w.dim() == 2 and w.shape[1] == 9 * Cin and Cout % 8 == 0
+    T = split16_empty(9 * Cin, Cout, w.device)
+    L().dupl_split_wT_tc(w.data_ptr(), w.stride(0), Cout, Cin, T.hi, T.lo, Cout, _stream())
+    return T
+
+
 def linear16(x, W: Split16, bias: Optional[Tensor] = None, *, gelu: bool = False, relu: bool = False,
              res: Optional[Tensor] = None, out: Optional[Tensor] = None, store_pre: Optional[Tensor] = None,
              want_f32: bool = True, out16: Optional[Split16] = None, want16: bool = False, device=None,

@@ -461,6 +461,21 @@ int dupl_im2col_dil3(const float* x, float* col, int32_t B, int32_t h, int32_t w
 /* adjoint (autograd of conv_head.py:34-39): dx (+)= gather of dcol, zeroed where relu_of (same layout as dx, post-ReLU activations) <= 0 if non-NULL */
 int dupl_col2im_dil3(const float* dcol, float* dx, int32_t B, int32_t h, int32_t w, int32_t Cin, int32_t dil, int64_t ld,
                      int64_t img_stride, int32_t accumulate, const float* relu_of, dupl_stream_t s);
+/* dupl_im2col_dil3 straight into the format 0 operand planes of dupl_gemm_f16x3 (no fp32 col): the same operand description
+ * (Cin % 8 == 0, ld and img_stride % 4 == 0, every pointer 16-byte aligned) -> row-major planes hi / lo [B*h*w][9*Cin] (column
+ * c*9 + tap; bit-equal to dupl_split_f16x2 of the fp32 col) and / or transposed planes hiT / loT [9*Cin][Mp] (Mp >= B*h*w,
+ * multiple of 8, rows B*h*w .. Mp-1 written as zeros; bit-equal to dupl_split_prepare's transposed planes of the fp32 col).
+ * Either pair may be NULL. */
+int dupl_im2col_dil3_planes(const float* x, void* hi, void* lo, void* hiT, void* loT, int32_t B, int32_t h, int32_t w,
+                            int32_t Cin, int32_t dil, int64_t ld, int64_t img_stride, int32_t Mp, dupl_stream_t s);
+/* dupl_col2im_dil3 on TAP-MAJOR columns: dcol [B*h*w][9*Cin] with column tap*Cin + c (Cin, ld, img_stride % 4 == 0, pointers
+ * 16-byte aligned).  Adds the taps in the order 0 .. 8 like dupl_col2im_dil3: on the column-permuted dcol the result is bit-equal. */
+int dupl_col2im_dil3_tc(const float* dcol, float* dx, int32_t B, int32_t h, int32_t w, int32_t Cin, int32_t dil, int64_t ld,
+                        int64_t img_stride, int32_t accumulate, const float* relu_of, dupl_stream_t s);
+/* transposed format 0 planes hiT / loT [9*Cin][Rp] (Rp >= Cout, multiple of 8, rows Cout.. zeros) of a conv weight w [Cout][ld]
+ * (9*Cin columns, c*9 + tap) with their ROWS in (tap, c) order: row tap*Cin + c holds what dupl_split_prepare writes at row
+ * c*9 + tap.  As the B operand of the data gradient dcol = dy . W it yields dcol in the column order dupl_col2im_dil3_tc reads. */
+int dupl_split_wT_tc(const float* w, int32_t ld, int32_t Cout, int32_t Cin, void* hiT, void* loT, int32_t Rp, dupl_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Optimiser (utils/optimizer.py:38-68 -> torch.optim.AdamW) and small element-wise helpers. */

@@ -38,6 +38,29 @@ def set_gemm_mode(mode: str):
     GEMM_MODE = mode
 
 
+# The no-grad encoder passes (_encoder_forward16(save=False): the multi-scale CAM passes of a step, validation, tools/infer_cam, the
+# encoder part of tools/eval_seg) may trade precision for rate: "f16" runs every site the RangeGuard leaves on planes -- patch
+# embedding, qkv, proj, fc1, fc2 and the attention -- as ONE f16 product on the hi planes with fp32 accumulation
+# (gemm_f16_ring16_kernel, attn_fwd16_h1_kernel) instead of three.  Opt-in (DUPL_NOGRAD_GEMM=f16 or set_nograd_gemm_mode); the
+# default "f16x3" changes nothing.  Applies only while GEMM_MODE == "f16x3"; a pass that saves anything for the backward, the CAM
+# heads and the LargeFOV convs never run single-product.
+NOGRAD_GEMM = os.environ.get("DUPL_NOGRAD_GEMM", "f16x3")
+if NOGRAD_GEMM not in ("f16", "f16x3"):
+    raise ValueError(f"DUPL_NOGRAD_GEMM={NOGRAD_GEMM!r}: expected 'f16' or 'f16x3'")
+
+
+def set_nograd_gemm_mode(mode: str):
+    global NOGRAD_GEMM
+    if mode not in ("f16", "f16x3"):
+        raise ValueError(f"nograd gemm mode {mode!r}: expected 'f16' or 'f16x3'")
+    NOGRAD_GEMM = mode
+
+
+def nograd_products(save: bool) -> int:
+    """dupl_gemm16_desc.products / the attention's `products` of an encoder pass: 1 only for a pass that saves nothing, under f16."""
+    return 1 if (not save and NOGRAD_GEMM == "f16" and GEMM_MODE == "f16x3") else 3
+
+
 @dataclass(frozen=True)
 class EncoderConfig:
     embed_dim: int = 768
@@ -714,6 +737,7 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
     W = P.w
     P.store.ensure_w16(P.student)
     guard = P.store.guard.sites(P.student)      # which sites may run on fp16 planes (RangeGuard); the others run on f32
+    prod = nograd_products(save)                # 1: the no-grad "f16" mode -- every plane site below as one product on the hi planes
     # save_rows > 0 (shared ms-CAM / training pass: rows of the un-flipped images come first and only they are back-propagated):
     # the fp32 copies the backward needs are produced for those rows only -- planes, which the forward consumes, for all rows.
     # Only while every site runs on planes (an f32-routed consumer needs its fp32 input for all rows).
@@ -733,7 +757,8 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
         if guard["patch"]:
             e = ea(guard, "patch")
             rows16 = ops.split16(ops.patch_im2row(x, cfg.patch), exp=e)
-            patch, _ = _lin16(P, rows16, P.w16("encoder.patch_embed.proj.weight", D, bool(e)), W["encoder.patch_embed.proj.bias"])
+            patch, _ = _lin16(P, rows16, P.w16("encoder.patch_embed.proj.weight", D, bool(e)), W["encoder.patch_embed.proj.bias"],
+                             products=prod)
             del rows16
         else:
             patch = ops.linear(ops.patch_im2row(x, cfg.patch), W["encoder.patch_embed.proj.weight"], W["encoder.patch_embed.proj.bias"])
@@ -768,7 +793,7 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
         need_qkv32 = (not attn16) or (save and groups[0][2] > 2048)       # (only batch 0 is ever back-propagated)
         if g["qkv"]:
             qkv, qkv16 = _lin16(P, ln1_16, P.w16(p + "attn.qkv.weight", 3 * D, bool(ln1_16.exp)), W[p + "attn.qkv.bias"],
-                                      want_f32=need_qkv32, want16=attn16)
+                                      want_f32=need_qkv32, want16=attn16, products=prod)
         else:
             qkv = ops.linear(ln1, W[p + "attn.qkv.weight"], W[p + "attn.qkv.bias"])
             qkv16 = ops.split16(qkv) if attn16 else None
@@ -787,17 +812,18 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
                 planes_only = bool(save_rows and gi > 0) or att is None
                 bf = save_rows // N if (save_rows and gi == 0) else 0
                 segs.append((g0, B, N, None if planes_only else att[g0:g0 + (bf or B) * N], bool(save and gi == 0), bf))
-            lse = ops.attention_fwd16_segs(qkv16, segs, H, hd, scale, out16=att16)[0]
+            lse = ops.attention_fwd16_segs(qkv16, segs, H, hd, scale, out16=att16, products=prod)[0]
         for gi, (g0, B, N, _, _) in enumerate(() if use_segs else groups):
             if attn16:
                 if save_rows and gi > 0:      # rows beyond the saved prefix: planes only, no fp32 output, no lse
                     ops.attention_fwd16(qkv16.rows_slice(g0, g0 + B * N), B, N, H, hd, scale, need_lse=False, out=None,
-                                        out16=att16.rows_slice(g0, g0 + B * N))
+                                        out16=att16.rows_slice(g0, g0 + B * N), products=prod)
                     continue
                 bf = save_rows // N if save_rows else 0
                 lse_g = ops.attention_fwd16(qkv16.rows_slice(g0, g0 + B * N), B, N, H, hd, scale, need_lse=save,
                                             out=att[g0:g0 + (bf or B) * N] if att is not None else None,
-                                            out16=att16.rows_slice(g0, g0 + B * N) if att16 is not None else None, b_f32=bf)
+                                            out16=att16.rows_slice(g0, g0 + B * N) if att16 is not None else None, b_f32=bf,
+                                            products=prod)
             else:   # other head dims (the 96-dim test backbone) or q / k / v beyond fp16's range: exact-f32 attention kernel
                 _, lse_g = ops.attention_fwd(qkv[g0:g0 + B * N], B, N, H, hd, scale, need_lse=save, out=att[g0:g0 + B * N])
             if gi == 0:
@@ -807,7 +833,7 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
         qkv16_keep = qkv16 if (save and attn16) else None
         del qkv16
         if g["proj"]:
-            x_mid, _ = _lin16(P, att16, P.w16(p + "attn.proj.weight", D, bool(att16.exp)), W[p + "attn.proj.bias"], res=t)
+            x_mid, _ = _lin16(P, att16, P.w16(p + "attn.proj.weight", D, bool(att16.exp)), W[p + "attn.proj.bias"], res=t, products=prod)
         else:
             x_mid = ops.linear(att, W[p + "attn.proj.weight"], W[p + "attn.proj.bias"], res=t)
         att_keep = att16 if (km["proj"] and att16 is not None and att16.exp > 0) else None
@@ -822,7 +848,7 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
             km["fc2"] = km["fc2"] and e2 > 0
             h1, h1_16 = _lin16(P, ln2_16, P.w16(p + "mlp.fc1.weight", D * cfg.mlp_ratio, bool(ln2_16.exp)), W[p + "mlp.fc1.bias"],
                                      gelu=True, store_pre=pre1, want_f32=(save and not km["fc2"]) or not g["fc2"], want16=g["fc2"],
-                                     c_rows=save_rows, out_exp=e2)
+                                     c_rows=save_rows, out_exp=e2, products=prod)
         else:
             h1 = ops.linear(ln2, W[p + "mlp.fc1.weight"], W[p + "mlp.fc1.bias"], gelu=True, store_pre=pre1)
             h1_16 = ops.split16(h1, exp=ea(g, "fc2")) if g["fc2"] else None
@@ -831,7 +857,7 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
         h1_keep = h1_16 if km["fc2"] else None
         del ln2_16
         if g["fc2"]:
-            x_out, _ = _lin16(P, h1_16, P.w16(p + "mlp.fc2.weight", D, bool(h1_16.exp)), W[p + "mlp.fc2.bias"], res=x_mid)
+            x_out, _ = _lin16(P, h1_16, P.w16(p + "mlp.fc2.weight", D, bool(h1_16.exp)), W[p + "mlp.fc2.bias"], res=x_mid, products=prod)
         else:
             x_out = ops.linear(h1, W[p + "mlp.fc2.weight"], W[p + "mlp.fc2.bias"], res=x_mid)
         del h1_16

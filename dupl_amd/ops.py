@@ -319,7 +319,8 @@ def linear16(x, W: Split16, bias: Optional[Tensor] = None, *, gelu: bool = False
              want_f32: bool = True, out16: Optional[Split16] = None, want16: bool = False, device=None,
              alpha: Optional[int] = None, accumulate: bool = False, dgelu_of: Optional[Tensor] = None,
              relumask_of: Optional[Tensor] = None, c_rows: int = 0, amax_for_next: bool = False, out_exp: int = 0,
-             a_kmajor: bool = False, b_kmajor: bool = False, k_pad: int = 0, post_exp: int = 0, tuning: Optional[dict] = None):
+             a_kmajor: bool = False, b_kmajor: bool = False, k_pad: int = 0, post_exp: int = 0, tuning: Optional[dict] = None,
+             products: int = 0):
     """y = act(alpha * x W^T + bias) (+ res) on the f16x3 split GEMM.  x: Split16 / Split16View [M, K]; W: Split16 [N, K].
     alpha: device pointer of a float (inverse scale of scaled gradient planes).  accumulate: out += alpha * x W^T (weight
     gradients; split-K).  dgelu_of / relumask_of: multiply by gelu'(pre) / (post > 0) (data gradients through an activation).
@@ -329,6 +330,8 @@ def linear16(x, W: Split16, bias: Optional[Tensor] = None, *, gelu: bool = False
     GEMMs on the forward's own planes.  k_pad: the contraction length the kernel walks (a multiple of 32, >= 96; operand rows
     beyond their own count are clamped, the other operand holds zeros there).  post_exp: the product carries 2^post_exp beyond the
     operands' exp (scaled gradient planes carry theirs in alpha).
+    products: dupl_gemm16_desc.products -- 0 / 3 = the f16x3 kernels, 1 = the single-product (hi planes only) forward kernel of the
+    no-grad "f16" mode (k-contiguous operands, no accumulate).
     Returns (y fp32 [M, N] or None, y as Split16 or None)."""
     M, Ka = (x.cols, x.rows) if a_kmajor else (x.rows, x.cols)
     N, Kb = (W.cols, W.rows) if b_kmajor else (W.rows, W.cols)
@@ -386,6 +389,7 @@ def linear16(x, W: Split16, bias: Optional[Tensor] = None, *, gelu: bool = False
     d.tile, d.concurrency = tn["tile"], tn["concurrency"]
     d.persist_blocks, d.group = tn["persist_blocks"], tn["group"]
     d.sk_slices = tn["sk_slices"]
+    d.products = int(products)
     tok = None
     if amax_for_next and y is not None and not accumulate and not c_rows:
         d.amax_out, tok = reserve_amax(dev)
@@ -596,8 +600,9 @@ ATTN16_TUNING = {"mfma": int(_os.environ.get("DUPL_ATTN16_MFMA", "0"))}
 
 
 def attention_fwd16(qkv16, B: int, N: int, H: int, hd: int, scale: float, need_lse: bool = False,
-                    out: Optional[Tensor] = None, out16=None, b_f32: int = 0):
-    """Attention forward on the f16x3 split kernels (head dim 64).  qkv16: Split16 / Split16View [B*N, 3*H*hd] (planes of
+                    out: Optional[Tensor] = None, out16=None, b_f32: int = 0, products: int = 3):
+    """Attention forward on the f16x3 split kernels (head dim 64); products = 1: the single-product kernel of the no-grad "f16" mode
+    (hi planes only, no lse).  qkv16: Split16 / Split16View [B*N, 3*H*hd] (planes of
     the qkv GEMM output); out: optional fp32 [B*N, H*hd] destination; out16: optional Split16 / Split16View [B*N, H*hd]
     receiving the planes of the output.  Returns lse (B, H, N) or None."""
     assert hd == 64 and qkv16.rows == B * N and qkv16.cols == 3 * H * hd and (out is not None or out16 is not None)
@@ -607,13 +612,14 @@ def attention_fwd16(qkv16, B: int, N: int, H: int, hd: int, scale: float, need_l
     if out is not None:
         assert out.shape == (bf * N, H * hd) and out.is_contiguous()
     assert getattr(qkv16, "exp", 0) == 0, "the split attention reads format 0 planes"
-    L().dupl_attention_fwd16_mfma(qkv16.hi, qkv16.lo, _p(out), out16.hi if out16 is not None else None,
+    L().dupl_attention_fwd16_prod(qkv16.hi, qkv16.lo, _p(out), out16.hi if out16 is not None else None,
                                    out16.lo if out16 is not None else None, _p(lse), B, N, H, hd, float(scale), bf,
-                                   out16.exp if out16 is not None else 0, ATTN16_TUNING["mfma"], _stream())
+                                   out16.exp if out16 is not None else 0, 0 if products == 1 else ATTN16_TUNING["mfma"], int(products),
+                                   _stream())
     return lse
 
 
-def attention_fwd16_segs(qkv16, segs, H: int, hd: int, scale: float, out16=None):
+def attention_fwd16_segs(qkv16, segs, H: int, hd: int, scale: float, out16=None, products: int = 3):
     """Split attention forward of SEVERAL batches that live in one token buffer, as ONE launch (dupl_attention_fwd16_segs).
     qkv16 / out16: planes of ALL rows; segs: [(row0, B, N, out fp32 [bf*N, H*hd] or None, need_lse, b_f32)] with bf = b_f32 or B.
     Returns the list of lse tensors (None where not asked for)."""
@@ -630,9 +636,10 @@ def attention_fwd16_segs(qkv16, segs, H: int, hd: int, scale: float, out16=None)
         lses.append(lse)
         arr[i].row0, arr[i].B, arr[i].N, arr[i].B_f32 = int(row0), int(B), int(N), int(b_f32)
         arr[i].out, arr[i].lse = _p(out), _p(lse)
-    L().dupl_attention_fwd16_segs_mfma(qkv16.hi, qkv16.lo, out16.hi if out16 is not None else None,
+    L().dupl_attention_fwd16_segs_prod(qkv16.hi, qkv16.lo, out16.hi if out16 is not None else None,
                                         out16.lo if out16 is not None else None, ctypes.cast(arr, ctypes.c_void_p), len(segs), H, hd,
-                                        float(scale), out16.exp if out16 is not None else 0, ATTN16_TUNING["mfma"], _stream())
+                                        float(scale), out16.exp if out16 is not None else 0,
+                                        0 if products == 1 else ATTN16_TUNING["mfma"], int(products), _stream())
     return lses
 
 

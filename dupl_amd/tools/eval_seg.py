@@ -178,6 +178,7 @@ def build_parser(dataset: str = "voc"):
     """The flags of tools/eval_seg_voc.py:26-36 (dataset "voc") or tools/eval_seg_coco_ddp.py:31-46 ("coco"): same names and
     defaults (tests/golden/cli_flags.json), plus --dataset, --save_logits and --crf."""
     import argparse
+    import os
     voc_ = dataset == "voc"
     p = argparse.ArgumentParser()
     p.add_argument("--dataset", default=dataset, choices=("voc", "coco"))
@@ -204,6 +205,10 @@ def build_parser(dataset: str = "voc"):
                    help="1: run the reference's crf_proc on the device after the inference (DenseCRF(10, 1, 1, 4, 121, 5) on the "
                         "better student's saved logits; needs --save_logits 1): prints the seg_crf table, writes "
                         "<run>/segs/seg_preds/<infer_set>/<name>.png (+ the palette PNGs)")
+    p.add_argument("--nograd_gemm", default=os.environ.get("DUPL_NOGRAD_GEMM", "f16x3"), choices=("f16x3", "f16"),
+                   help="GEMMs and attention of the no-grad encoder passes (multi-scale CAM, validation, inference): f16x3 = three f16 products, "
+                        "fp32-equivalent (default); f16 = one product on the hi planes, fp32 accumulation (engine.set_nograd_gemm_mode; "
+                        "experimental)")
     return p
 
 
@@ -224,6 +229,8 @@ def main(argv=None):
     pre.add_argument("--dataset", default="voc", choices=("voc", "coco"))
     is_voc = pre.parse_known_args(argv)[0].dataset == "voc"
     args = build_parser("voc" if is_voc else "coco").parse_args(argv)
+    from .. import engine
+    engine.set_nograd_gemm_mode(args.nograd_gemm)
     if isinstance(args.scales, str):
         args.scales = [float(v) for v in args.scales.strip("()[] ").split(",")]
     args.scales = tuple(args.scales)

@@ -42,7 +42,17 @@ def build_parser():
     p.add_argument("--save_img", default=1, type=int, help="write the jet overlays to cam_img/ and cam_img_aux/")
     p.add_argument("--save_labels", default=0, type=int,
                    help="write the label map at --bkg_thre to cam_labels/<set>/<name>.png (+ cam_labels_rgb/)")
+    # (no attribute unless given: the namespace of a plain run stays the reference's flag set; nograd_gemm_mode() supplies the default)
+    p.add_argument("--nograd_gemm", default=argparse.SUPPRESS, choices=("f16x3", "f16"),
+                   help="GEMMs and attention of the no-grad encoder passes (multi-scale CAM, validation, inference): f16x3 = three f16 products, "
+                        "fp32-equivalent (default); f16 = one product on the hi planes, fp32 accumulation (engine.set_nograd_gemm_mode; "
+                        "experimental)")
     return p
+
+
+def nograd_gemm_mode(args) -> str:
+    """--nograd_gemm of a parsed command line; when the flag was not given, DUPL_NOGRAD_GEMM or f16x3."""
+    return getattr(args, "nograd_gemm", os.environ.get("DUPL_NOGRAD_GEMM", "f16x3"))
 
 
 def parse_scales(text):
@@ -112,6 +122,8 @@ def main(argv=None):
     from ..model.model_dupl import siamese_network
     from ..utils import imutils
     args = build_parser().parse_args(argv)
+    from .. import engine
+    engine.set_nograd_gemm_mode(nograd_gemm_mode(args))
     thresholds, at = sweep_thresholds(args.sweep, args.bkg_thre)
     local = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -81,6 +81,10 @@ def build_parser(dataset: str) -> argparse.ArgumentParser:
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible steps (dupl_amd.set_deterministic): what cudnn.deterministic = True asks for in "
                         "the reference's setup_seed (train_final_voc.py:95-102); costs ~20 %% throughput")
+    p.add_argument("--nograd_gemm", default=os.environ.get("DUPL_NOGRAD_GEMM", "f16x3"), choices=("f16x3", "f16"),
+                   help="GEMMs and attention of the no-grad encoder passes (multi-scale CAM, validation, inference): f16x3 = three f16 products, "
+                        "fp32-equivalent (default); f16 = one product on the hi planes, fp32 accumulation (engine.set_nograd_gemm_mode; "
+                        "experimental)")
     return p
 
 
@@ -268,6 +272,8 @@ def train(args, dataset: str, loader=None, val_loader=None):
     if getattr(args, "deterministic", False):
         import dupl_amd
         dupl_amd.set_deterministic(True)
+    from . import engine as _engine
+    _engine.set_nograd_gemm_mode(getattr(args, "nograd_gemm", _engine.NOGRAD_GEMM))
     distributed = int(os.environ.get("WORLD_SIZE", "1")) > 1
     if distributed:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")

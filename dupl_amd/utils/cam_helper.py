@@ -48,7 +48,9 @@ def _ms_cam(P, inputs, scales, share=None):
                 # chosen from them (a site that turns f32-routed at this step -- a harvest, a rewritten parameter -- would otherwise
                 # meet a merged pass that can no longer save a row prefix)
                 P.store.ensure_w16(P.student)
-            if len(xs) > 1 and rows_all <= engine.MERGED_PASS and engine.partial_save_ok(P):
+            # (the no-grad "f16" mode takes the two-pass form: one pass cannot mix single-product and f16x3 rows -- the scale-1.0
+            # pass, flipped half included, stays f16x3 because it saves for the backward; the other scales run single-product)
+            if len(xs) > 1 and rows_all <= engine.MERGED_PASS and engine.partial_save_ok(P) and engine.nograd_products(False) == 3:
                 # round 5: every scale AND the training forward in one encoder pass (21 976 token rows at 448^2, 4 images)
                 res, share["enc"] = engine.cam_logits_shared_multi(P, xs, b)
             else:

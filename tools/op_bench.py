@@ -1,11 +1,16 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] | backbone
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] | backbone | nograd
 `crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81.
 `cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces.
 `backbone` (only when named; then nothing else runs) times one phase-B training step at VOC 448^2, 4 images, two student streams
 for every registered --backbone, or for the names that follow it: bench.py's own workload and timed region (bench.Workload.measure:
 warm-up steps, then K steps between synchronisations), so the deit_base_patch16_224 row is bench.py's figure.
-    python tools/op_bench.py backbone [name ...] [steps=20] [warmup=5]"""
+    python tools/op_bench.py backbone [name ...] [steps=20] [warmup=5]
+`nograd` (only when named; then nothing else runs) times the merged no-grad ms-CAM pass of one ViT-B student at the bench shape
+(engine.cam_logits_multi on 8 x 224^2 + 8 x 672^2: the 0.5x and 1.5x scales of 4 images at 448^2, flipped copies included) in both
+modes of engine.set_nograd_gemm_mode, interleaved in one process, and prints what the single-product mode changes in the result:
+the max-abs difference of the normalised multi-scale CAMs and the number of cam_to_label pixels that differ, 448^2, 4 images,
+seeded synthetic batch and seeded random weights (no pretrained checkpoint: the accuracy on trained weights is not measured)."""
 import gc
 import sys
 
@@ -128,9 +133,52 @@ def backbone_bench(argv):
         print(f"| `{name}` | {cfg.embed_dim} | {cfg.depth} | {cfg.num_heads} | {cfg.grid} x {cfg.grid} | {ms:.2f} | {v:.2f} |")
 
 
+def nograd_bench(argv):
+    from dupl_amd import engine
+    from dupl_amd.model.model_dupl import network
+    from dupl_amd.synthetic import synthetic_batch
+    from dupl_amd.utils import cam_helper
+    opts = dict(a.split("=", 1) for a in argv if "=" in a)
+    n, rounds = int(opts.get("n", 10)), int(opts.get("rounds", 3))
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    net = network("deit_base_patch16_224", num_classes=21, pretrained=False, aux_layer=-3).to(dev).eval()
+    inputs, cls_label, _ = synthetic_batch(4, 20, 448, seed=0)
+    inputs, cls_label = inputs.to(dev), cls_label.to(dev).float()
+    xs = [ops.resize_bilinear(inputs, s, s, flip_cat=True) for s in (224, 672)]
+    rows = sum(x.shape[0] * ((x.shape[2] // 16) ** 2 + 1) for x in xs)
+    times = {"f16x3": [], "f16": []}
+    with torch.no_grad():
+        for r in range(rounds):           # the two modes interleaved: both see the same clocks and temperature
+            for mode in ("f16x3", "f16"):
+                engine.set_nograd_gemm_mode(mode)
+                times[mode].append(timeit(lambda: engine.cam_logits_multi(net._P, xs), n=n, warm=3 if r == 0 else 1) / 1e3)
+        for mode in ("f16x3", "f16"):
+            t = sorted(times[mode])
+            print(f"nograd {mode}: cam_logits_multi, {rows} token rows (8 x 224^2 + 8 x 672^2), ViT-B: median {t[len(t) // 2]:.2f} ms "
+                  f"(rounds of {n}: {', '.join(f'{v:.2f}' for v in times[mode])})")
+        m3, m1 = sorted(times["f16x3"])[rounds // 2], sorted(times["f16"])[rounds // 2]
+        print(f"nograd f16 / f16x3 = {m1 / m3:.3f}")
+        res = {}
+        for mode in ("f16x3", "f16"):
+            engine.set_nograd_gemm_mode(mode)
+            cam, cam_aux = cam_helper.multi_scale_cam2(net, inputs, (1.0, 0.5, 1.5))
+            res[mode] = (cam, cam_aux, cam_helper.cam_to_label(cam, cls_label, bkg_thre=0.45),
+                         cam_helper.cam_to_label(cam_aux, cls_label, bkg_thre=0.45))
+        engine.set_nograd_gemm_mode("f16x3")
+    a, b = res["f16x3"], res["f16"]
+    npx = a[2].numel()
+    print(f"nograd CAM (448^2, 4 images, scales 1.0 / 0.5 / 1.5, normalised to [0, 1)): max-abs-diff cam {float((a[0] - b[0]).abs().max()):.3e}, "
+          f"cam_aux {float((a[1] - b[1]).abs().max()):.3e}; cam_to_label (bkg_thre 0.45) pixels that differ: cam {int((a[2] != b[2]).sum())}, "
+          f"cam_aux {int((a[3] != b[3]).sum())} of {npx}")
+    print("guard:", net._store.guard.summary())
+
+
 def main():
     if "backbone" in sys.argv[1:]:
         return backbone_bench(sys.argv[1:])
+    if "nograd" in sys.argv[1:]:
+        return nograd_bench(sys.argv[1:])
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)

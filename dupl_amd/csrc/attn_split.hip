@@ -27,6 +27,7 @@
 //       has one permlane32_swap).  Same DMA protocol, segments, remap, outputs and f16x3 arithmetic; the sums differ from the
 //       32x32x16 body's in the last bits (accumulation order).  Why: under this loop the chip holds its clock down, and at equal
 //       MFMA cycles the 16x16x32 shape draws less (profiles/mfma16_attn.txt: -10 % per launch at 8 x 1765).
+//       A template on the product count: <3> is the above, <1> the single-product form (products = 1; described at the kernel).
 #include "split_frag.h"
 #include "../../include/dupl_hip.h"
 
@@ -55,6 +56,15 @@ struct AttnSegs {
     float* lse[DUPL_ATTN_SEGS_MAX];
 };
 
+// ---- shared by the forward kernels
+// The planes of a launch, moved to the segment's first token row r0 (a plane the kernel never reads may be passed as NULL).
+template <class In, class Out>      // (the kernels' __restrict__ pointers)
+__device__ __forceinline__ void attn_seg_planes(const size_t r0, const int H, In& qkv_hi, In& qkv_lo, Out& out_hi, Out& out_lo) {
+    qkv_hi += r0 * (size_t)(3 * H * HD);
+    qkv_lo += r0 * (size_t)(3 * H * HD);
+    if (out_hi) { out_hi += r0 * (size_t)(H * HD); out_lo += r0 * (size_t)(H * HD); }
+}
+
 __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __restrict__ qkv_hi, const __half* __restrict__ qkv_lo,
                                                             __half* __restrict__ out_hi, __half* __restrict__ out_lo,
                                                             const AttnSegs segs, int H, float scale, int remap, float out_scale) {
@@ -76,12 +86,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
         const int w = remap ? xcd_band(L, G) : L;      // whole heads per XCD inside the segment
         bx = w % gx; h = (w / gx) % H; b = w / (gx * H);
     }
-    {
-        const size_t r0 = (size_t)segs.row0[sg];
-        qkv_hi += r0 * (size_t)(3 * H * HD);
-        qkv_lo += r0 * (size_t)(3 * H * HD);
-        if (out_hi) { out_hi += r0 * (size_t)(H * HD); out_lo += r0 * (size_t)(H * HD); }
-    }
+    attn_seg_planes((size_t)segs.row0[sg], H, qkv_hi, qkv_lo, out_hi, out_lo);
     const int q0 = bx * 128 + wave * 32;
     const int D = H * HD, ld = 3 * D;
     const int qrow = q0 + l31;
@@ -165,9 +170,10 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
 
     const int nkt = (N + KT - 1) / KT;
     long long tph[4] = {0, 0, 0, 0}, tlast = 0;      // ATT_ABL & 16: wait + barrier, QK, softmax, PV
-    if (ATT_ABL & 16) tlast = clock64();
+    constexpr bool ABL16 = ATT_ABL & 16;
+    if (ABL16) tlast = clock64();
 #define ATT_STAMP(i)                                  \
-    if (ATT_ABL & 16) {                               \
+    if (ABL16) {                                      \
         const long long now_ = clock64();             \
         tph[i] += now_ - tlast;                       \
         tlast = now_;                                 \
@@ -363,19 +369,32 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_kernel(const __half* __rest
 //   * O^T: oM / oX[dt][ct] hold d = 16 dt + 4 g .. + 3 of query 16 ct + c.
 //   * softmax: a query's keys sit in its four lanes g.  The common path works on per-lane partial maxima and partial row sums only
 //     (no cross-lane operation); the four lanes are combined inside `move` (maximum) and once in the epilogue (row sum).
+// NP = 3 is the f16x3 arithmetic above.  NP = 1 is its single-product form (dupl_attention_fwd16_prod, products = 1: the opt-in "f16"
+// mode of the no-grad encoder passes): S = q_hi k_hi^T, the same fp32 softmax with the same lazy running maximum, the probabilities
+// rounded to ONE fp16 plane (p <= 2^8 under the lazy maximum: far inside fp16's range; the row sum is taken before the rounding),
+// O = P_hi v_hi -- 32 MFMAs per key tile and wave instead of 96.  Only the hi plane of qkv is fetched (qkv_lo is never read): a stage
+// is K_hi | V_hi (16 KB), laid out, swizzled and read exactly as the hi images of the NP = 3 stage.  No lse (no-grad only), and the
+// ATT_ABL / ATT_PRIO build knobs act on NP = 3 alone.  Everything marked X below (the lo plane, the cross terms) exists for NP = 3 only.
+template <int NP>
 __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __restrict__ qkv_hi, const __half* __restrict__ qkv_lo,
                                                                 __half* __restrict__ out_hi, __half* __restrict__ out_lo,
                                                                 const AttnSegs segs, int H, float scale, int remap, float out_scale) {
+    static_assert(NP == 1 || NP == 3, "one product or the three of f16x3");
+    constexpr bool X = NP == 3;              // lo planes and cross terms
+    constexpr int PL = X ? 2 : 1;            // planes per operand
+    constexpr int STAGE = 2 * PL * PLANE;    // K planes | V planes
+    constexpr bool ABL16 = X && (ATT_ABL & 16);
     __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE];
     const int tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, g4 = lane >> 4;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    // (segment search and block decode as in attn_fwd16_kernel, written out: as helpers they reorder both kernels' set-up)
     int sg = 0;
 #pragma unroll 1
     while (sg + 1 < segs.n && (int)blockIdx.x >= segs.first[sg + 1]) ++sg;
     sg = __builtin_amdgcn_readfirstlane(sg);
     const int N = segs.N[sg], B_f32 = segs.B_f32[sg];
     float* __restrict__ out = segs.out[sg];
-    float* __restrict__ lse = segs.lse[sg];
+    float* __restrict__ lse = X ? segs.lse[sg] : nullptr;
     int bx, h, b;
     {
         const int gx = (N + 127) / 128;
@@ -384,25 +403,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
         const int w = remap ? xcd_band(L, G) : L;
         bx = w % gx; h = (w / gx) % H; b = w / (gx * H);
     }
-    {
-        const size_t r0 = (size_t)segs.row0[sg];
-        qkv_hi += r0 * (size_t)(3 * H * HD);
-        qkv_lo += r0 * (size_t)(3 * H * HD);
-        if (out_hi) { out_hi += r0 * (size_t)(H * HD); out_lo += r0 * (size_t)(H * HD); }
-    }
+    attn_seg_planes((size_t)segs.row0[sg], H, qkv_hi, qkv_lo, out_hi, out_lo);
     const int q0 = bx * 128 + wave * 32;
     const int D = H * HD, ld = 3 * D;
     const bool wave_active = q0 < N;
 
-    // ---- Q fragments (B operand): lane (c, g) holds Q[q0 + 16 ct + c][32 ks + 8 g .. + 7], both planes
-    h8 qh[2][2], ql[2][2];                   // [ct][ks]
+    // ---- Q fragments (B operand): lane (c, g) holds Q[q0 + 16 ct + c][32 ks + 8 g .. + 7], every plane
+    h8 qh[2][2], ql[2][2];                   // [ct][ks]; ql: X
 #pragma unroll
     for (int ct = 0; ct < 2; ++ct) {
         const size_t off = ((size_t)b * N + min(q0 + 16 * ct + c16, N - 1)) * ld + h * HD + 8 * g4;
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             qh[ct][ks] = load_bfrag(qkv_hi + off, 2 * ks);
-            ql[ct][ks] = load_bfrag(qkv_lo + off, 2 * ks);
+            if constexpr (X) ql[ct][ks] = load_bfrag(qkv_lo + off, 2 * ks);
         }
     }
 
@@ -435,16 +449,16 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
         const size_t o = t * tstride;
         if (t * KT + KT <= N) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dma16o(kbase[i >> 1] + o, koff[i & 1], dst + i * 4096);
+            for (int i = 0; i < 2 * PL; ++i) dma16o(kbase[i >> 1] + o, koff[i & 1], dst + i * 4096);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) dma16o(vbase[i >> 1] + o, voff[i & 1], dst + (4 + i) * 4096);
+            for (int i = 0; i < 2 * PL; ++i) dma16o(vbase[i >> 1] + o, voff[i & 1], dst + (2 * PL + i) * 4096);
         } else {
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
+            for (int i = 0; i < 2 * PL; ++i)
                 dma16o(kbase[i >> 1] + o, (unsigned)(min(t * KT + krow[i & 1], N - 1) - t * KT) * (unsigned)(ld * 2) + kch[i & 1], dst + i * 4096);
 #pragma unroll
-            for (int i = 0; i < 4; ++i)
-                dma16o(vbase[i >> 1] + o, (unsigned)(min(t * KT + vrow[i & 1], N - 1) - t * KT) * (unsigned)(ld * 2) + vch, dst + (4 + i) * 4096);
+            for (int i = 0; i < 2 * PL; ++i)
+                dma16o(vbase[i >> 1] + o, (unsigned)(min(t * KT + vrow[i & 1], N - 1) - t * KT) * (unsigned)(ld * 2) + vch, dst + (2 * PL + i) * 4096);
         }
     };
 
@@ -453,9 +467,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
     // and the swizzle of these rows depends on c alone: one lane offset, (G, j) immediates, ks one XOR
     const int k_off = pi16_row(c16, 0) * 128 + ((g4 ^ rm16_swizzle(pi16_row(c16, 0))) * 16);
     // V: read (key step S, half jj, d tile dt) takes subtile (S * 2 + jj) * 4 + dt by km_tr_read
-    const unsigned v_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem) + 2 * PLANE + km16_read_lane_off(lane);
+    const unsigned v_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem) + PL * PLANE + km16_read_lane_off(lane);
 
-    f32x4 oM[4][2], oX[4][2];                // [dt][ct]
+    f32x4 oM[4][2], oX[4][2];                // [dt][ct]; oX: X
 #pragma unroll
     for (int d = 0; d < 4; ++d)
 #pragma unroll
@@ -464,7 +478,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
 
     const int nkt = (N + KT - 1) / KT;
     long long tph[4] = {0, 0, 0, 0}, tlast = 0;
-    if (ATT_ABL & 16) tlast = clock64();
+    if (ABL16) tlast = clock64();
     issue(0, 0);
     for (int t = 0; t < nkt; ++t) {
         // the wait is written out on every path, idle waves included: see attn_fwd16_kernel
@@ -477,19 +491,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
 
         // ---- S^T = K Q^T in four steps (G, ks) = (0, 0), (0, 1), (1, 0), (1, 1); fragment reads one step ahead; the twelve MFMAs
         // of a step walk the four accumulators of the group three times (main, hi x lo, lo x hi): none is touched twice in a row
-        f32x4 sM[2][2][2], sX[2][2][2];      // [G][j][ct]
+        // (NP = 1: the four main MFMAs)
+        f32x4 sM[2][2][2], sX[2][2][2];      // [G][j][ct]; sX: X
         const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-        h8 kh[2][2], kl[2][2];               // [set][j]
+        h8 kh[2][2], kl[2][2];               // [set][j]; kl: X
         auto k_read = [&](const int step, h8(&fh)[2], h8(&fl)[2]) __attribute__((always_inline)) {
             const int a = (k_off ^ ((step & 1) * 64)) + (step >> 1) * 4096;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 fh[j] = *reinterpret_cast<const h8*>(st + a + j * 512);
-                fl[j] = *reinterpret_cast<const h8*>(st + PLANE + a + j * 512);
+                if constexpr (X) fl[j] = *reinterpret_cast<const h8*>(st + PLANE + a + j * 512);
             }
         };
         k_read(0, kh[0], kl[0]);
-        __builtin_amdgcn_s_setprio(ATT_PRIO);
+        if constexpr (X) __builtin_amdgcn_s_setprio(ATT_PRIO);
 #pragma unroll
         for (int step = 0; step < 4; ++step) {
             const int cur = step & 1, G = step >> 1, ks = step & 1;
@@ -499,18 +514,20 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) sM[G][j][ct] = MFMA_16x16x32(kh[cur][j], qh[ct][ks], ks == 0 ? zero4 : sM[G][j][ct]);
+            if constexpr (X) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+                for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int ct = 0; ct < 2; ++ct) sX[G][j][ct] = MFMA_16x16x32(kh[cur][j], ql[ct][ks], ks == 0 ? zero4 : sX[G][j][ct]);
+                    for (int ct = 0; ct < 2; ++ct) sX[G][j][ct] = MFMA_16x16x32(kh[cur][j], ql[ct][ks], ks == 0 ? zero4 : sX[G][j][ct]);
 #pragma unroll
-            for (int j = 0; j < 2; ++j)
+                for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int ct = 0; ct < 2; ++ct) sX[G][j][ct] = MFMA_16x16x32(kl[cur][j], qh[ct][ks], sX[G][j][ct]);
+                    for (int ct = 0; ct < 2; ++ct) sX[G][j][ct] = MFMA_16x16x32(kl[cur][j], qh[ct][ks], sX[G][j][ct]);
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
-        __builtin_amdgcn_s_setprio(0);
-        if (ATT_ABL & 16) {
+        if constexpr (X) __builtin_amdgcn_s_setprio(0);
+        if (ABL16) {
 #pragma unroll
             for (int G = 0; G < 2; ++G)
 #pragma unroll
@@ -518,12 +535,12 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
         }
         ATT_STAMP(1)
         // the first V^T fragments are fetched now: their LDS latency hides under the softmax arithmetic.  A PV step is (key step S,
-        // d tile pair dh): 8 reads = plane x d tile x half, 12 MFMAs
-        h4 vf[2][8];                         // [set][(plane * 2 + d tile of the pair) * 2 + half]
+        // d tile pair dh): 4 PL reads = plane x d tile x half, 4 NP MFMAs
+        h4 vf[2][4 * PL];                         // [set][(plane * 2 + d tile of the pair) * 2 + half]
         const unsigned v_st = v_lds + (t & 1) * STAGE;
-        auto v_read = [&](auto hc, h4(&f)[8]) __attribute__((always_inline)) {
+        auto v_read = [&](auto hc, h4(&f)[4 * PL]) __attribute__((always_inline)) {
             constexpr int HS = decltype(hc)::value, S = HS >> 1, DH = HS & 1;
-            static_for<8>([&](auto ic) __attribute__((always_inline)) {
+            static_for<4 * PL>([&](auto ic) __attribute__((always_inline)) {
                 constexpr int i = decltype(ic)::value, pl = i >> 2, dd = (i >> 1) & 1, jj = i & 1;
                 f[i] = km_tr_read<pl * PLANE + ((S * 2 + jj) * 4 + 2 * DH + dd) * 512>(v_st);
             });
@@ -570,10 +587,13 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
                 m_run[ct] = m2;
                 l_run[ct] *= alpha;
 #pragma unroll
-                for (int d = 0; d < 4; ++d) { oM[d][ct] *= alpha; oX[d][ct] *= alpha; }
+                for (int d = 0; d < 4; ++d) {
+                    oM[d][ct] *= alpha;
+                    if constexpr (X) oX[d][ct] *= alpha;
+                }
             }
         }
-        h8 ph[2][2], pl[2][2];               // [key step G][ct]
+        h8 ph[2][2], pl[2][2];               // [key step G][ct]; pl: X
 #pragma unroll
         for (int ct = 0; ct < 2; ++ct) {
             const float m_new = m_run[ct] == -INFINITY ? 0.f : m_run[ct];      // the guard of attn_fwd16_kernel
@@ -584,36 +604,47 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
                     for (int i = 0; i < 4; i += 2) {
-                        const f32x2 m2 = {sM[G][j][ct][i], sM[G][j][ct][i + 1]}, x2 = {sX[G][j][ct][i], sX[G][j][ct][i + 1]};
-                        const f32x2 v2 = __builtin_elementwise_fma(x2, f32x2{c2, c2}, __builtin_elementwise_fma(m2, f32x2{c1, c1}, f32x2{-m_new, -m_new}));
+                        const f32x2 m2 = {sM[G][j][ct][i], sM[G][j][ct][i + 1]};
+                        f32x2 v2;
+                        if constexpr (X) {
+                            const f32x2 x2 = {sX[G][j][ct][i], sX[G][j][ct][i + 1]};
+                            v2 = __builtin_elementwise_fma(x2, f32x2{c2, c2}, __builtin_elementwise_fma(m2, f32x2{c1, c1}, f32x2{-m_new, -m_new}));
+                        } else v2 = __builtin_elementwise_fma(m2, f32x2{c1, c1}, f32x2{-m_new, -m_new});
                         const f32x2 p2 = {__builtin_amdgcn_exp2f(v2[0]), __builtin_amdgcn_exp2f(v2[1])};
                         psum2 += p2;
-                        split_pair(p2, ph[G][ct], pl[G][ct], 4 * j + i);
+                        if constexpr (X) split_pair(p2, ph[G][ct], pl[G][ct], 4 * j + i);
+                        else {
+                            const h2v hh = __builtin_convertvector(p2, h2v);       // one packed convert, round to nearest even
+                            ph[G][ct][4 * j + i] = hh[0];
+                            ph[G][ct][4 * j + i + 1] = hh[1];
+                        }
                     }
             l_run[ct] += psum2[0] + psum2[1];
         }
-        if (ATT_ABL & 16) {
+        if (ABL16) {
             asm volatile("" ::"v"(ph[0][0]), "v"(ph[1][1]), "v"(pl[0][0]), "v"(pl[1][1]), "v"(oM[0][0]), "v"(oX[3][1]));
         }
         ATT_STAMP(2)
         // ---- O^T += V^T P^T, same read-ahead and accumulator rotation
-        __builtin_amdgcn_s_setprio(ATT_PRIO);
+        if constexpr (X) __builtin_amdgcn_s_setprio(ATT_PRIO);
         static_for<4>([&](auto hc) __attribute__((always_inline)) {
             constexpr int hs = decltype(hc)::value, cur = hs & 1, S = hs >> 1, d0 = 2 * (hs & 1);
             if constexpr (hs + 1 < 4) {
                 v_read(std::integral_constant<int, hs + 1>{}, vf[cur ^ 1]);
-                asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");       // LDS returns in order: the 8 reads of step hs have landed
+                if constexpr (X) asm volatile("s_waitcnt lgkmcnt(8)" ::: "memory");
+                else asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");       // LDS returns in order: the 8 reads of step hs have landed
             } else {
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             }
             __builtin_amdgcn_sched_barrier(0);
-            const h4(&f)[8] = vf[cur];
+            const h4(&f)[4 * PL] = vf[cur];
             const h8 vh0 = __builtin_shufflevector(f[0], f[1], 0, 1, 2, 3, 4, 5, 6, 7), vh1 = __builtin_shufflevector(f[2], f[3], 0, 1, 2, 3, 4, 5, 6, 7);
-            const h8 vl0 = __builtin_shufflevector(f[4], f[5], 0, 1, 2, 3, 4, 5, 6, 7), vl1 = __builtin_shufflevector(f[6], f[7], 0, 1, 2, 3, 4, 5, 6, 7);
             oM[d0][0] = MFMA_16x16x32(vh0, ph[S][0], oM[d0][0]);
             oM[d0][1] = MFMA_16x16x32(vh0, ph[S][1], oM[d0][1]);
             oM[d0 + 1][0] = MFMA_16x16x32(vh1, ph[S][0], oM[d0 + 1][0]);
             oM[d0 + 1][1] = MFMA_16x16x32(vh1, ph[S][1], oM[d0 + 1][1]);
+            if constexpr (X) {
+                const h8 vl0 = __builtin_shufflevector(f[4], f[5], 0, 1, 2, 3, 4, 5, 6, 7), vl1 = __builtin_shufflevector(f[6], f[7], 0, 1, 2, 3, 4, 5, 6, 7);
             oX[d0][0] = MFMA_16x16x32(vh0, pl[S][0], oX[d0][0]);
             oX[d0][1] = MFMA_16x16x32(vh0, pl[S][1], oX[d0][1]);
             oX[d0 + 1][0] = MFMA_16x16x32(vh1, pl[S][0], oX[d0 + 1][0]);
@@ -622,16 +653,17 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
             oX[d0][1] = MFMA_16x16x32(vl0, ph[S][1], oX[d0][1]);
             oX[d0 + 1][0] = MFMA_16x16x32(vl1, ph[S][0], oX[d0 + 1][0]);
             oX[d0 + 1][1] = MFMA_16x16x32(vl1, ph[S][1], oX[d0 + 1][1]);
+            }
             __builtin_amdgcn_sched_barrier(0);
         });
-        __builtin_amdgcn_s_setprio(0);
-        if (ATT_ABL & 16) {
+        if constexpr (X) __builtin_amdgcn_s_setprio(0);
+        if (ABL16) {
 #pragma unroll
             for (int d = 0; d < 4; ++d) asm volatile("" ::"v"(oM[d][0]), "v"(oM[d][1]), "v"(oX[d][0]), "v"(oX[d][1]));
         }
         ATT_STAMP(3)
     }
-    if ((ATT_ABL & 16) && lse && tid == 0) {
+    if ((ABL16) && lse && tid == 0) {
         long long* q = reinterpret_cast<long long*>(lse + (((size_t)segs.B[sg] * H * N + 1) & ~(size_t)1)) +
                        (size_t)((int)blockIdx.x - segs.first[sg]) * 4;
         q[0] = tph[0]; q[1] = tph[1]; q[2] = tph[2]; q[3] = tph[3];
@@ -651,7 +683,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
             for (int d = 0; d < 4; ++d) {             // a query's four lanes write 64 contiguous bytes (fp32) per instruction
                 float v[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = (oM[d][ct][j] + oX[d][ct][j] * LO_INV) * inv;
+                for (int j = 0; j < 4; ++j) v[j] = (X ? oM[d][ct][j] + oX[d][ct][j] * LO_INV : oM[d][ct][j]) * inv;
                 const int col = 16 * d + 4 * g4;
                 if (out) *reinterpret_cast<float4*>(out + ro + col) = make_float4(v[0], v[1], v[2], v[3]);
                 if (out_hi) {
@@ -670,244 +702,6 @@ __global__ __launch_bounds__(256, 2) void attn_fwd16_m16_kernel(const __half* __
     }
 }
 
-// The single-product form of attn_fwd16_m16_kernel (dupl_attention_fwd16_prod, products = 1: the opt-in "f16" mode of the no-grad
-// encoder passes): S = q_hi k_hi^T, the same fp32 softmax with the same lazy running maximum, the probabilities rounded to ONE fp16
-// plane (p <= 2^8 under the lazy maximum: far inside fp16's range), O = P_hi v_hi -- 32 MFMAs per key tile and wave instead of 96.
-// Only the hi plane of qkv is fetched: a stage is K_hi | V_hi (16 KB), laid out, swizzled and read exactly as the hi images there.
-// The row sum is taken over the fp32 probabilities, before the rounding.  No lse (no-grad only).  Block, segments, remap, DMA
-// protocol, key masking and outputs are the model's.
-__global__ __launch_bounds__(256, 2) void attn_fwd16_h1_kernel(const __half* __restrict__ qkv_hi, __half* __restrict__ out_hi,
-                                                               __half* __restrict__ out_lo, const AttnSegs segs, int H, float scale,
-                                                               int remap, float out_scale) {
-    constexpr int STAGE1 = 2 * PLANE;        // K_hi | V_hi
-    __shared__ __attribute__((aligned(1024))) char smem[2 * STAGE1];
-    const int tid = threadIdx.x, lane = tid & 63, c16 = lane & 15, g4 = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    int sg = 0;
-#pragma unroll 1
-    while (sg + 1 < segs.n && (int)blockIdx.x >= segs.first[sg + 1]) ++sg;
-    sg = __builtin_amdgcn_readfirstlane(sg);
-    const int N = segs.N[sg], B_f32 = segs.B_f32[sg];
-    float* __restrict__ out = segs.out[sg];
-    int bx, h, b;
-    {
-        const int gx = (N + 127) / 128;
-        const int G = gx * H * segs.B[sg];
-        const int L = (int)blockIdx.x - segs.first[sg];
-        const int w = remap ? xcd_band(L, G) : L;
-        bx = w % gx; h = (w / gx) % H; b = w / (gx * H);
-    }
-    {
-        const size_t r0 = (size_t)segs.row0[sg];
-        qkv_hi += r0 * (size_t)(3 * H * HD);
-        if (out_hi) { out_hi += r0 * (size_t)(H * HD); out_lo += r0 * (size_t)(H * HD); }
-    }
-    const int q0 = bx * 128 + wave * 32;
-    const int D = H * HD, ld = 3 * D;
-    const bool wave_active = q0 < N;
-
-    // ---- Q fragments (B operand): lane (c, g) holds Q[q0 + 16 ct + c][32 ks + 8 g .. + 7]
-    h8 qh[2][2];                             // [ct][ks]
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-        const size_t off = ((size_t)b * N + min(q0 + 16 * ct + c16, N - 1)) * ld + h * HD + 8 * g4;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) qh[ct][ks] = load_bfrag(qkv_hi + off, 2 * ks);
-    }
-
-    // ---- DMA plan: pieces wave and wave + 4 of the K and of the V image
-    const int prow = lane >> 3;
-    const char* kbase = reinterpret_cast<const char*>(qkv_hi + (size_t)b * N * ld + D + h * HD);
-    const char* vbase = kbase + D * 2;
-    int krow[2], kch[2], vrow[2];
-    const int vch = km16_piece_col_bytes(wave, lane);            // the same for pieces wave and wave + 4
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-        krow[j] = 8 * (wave + 4 * j) + prow;
-        kch[j] = rm16_piece_col_bytes(lane, krow[j]);
-        vrow[j] = km16_piece_row(wave + 4 * j, lane);
-    }
-    const size_t tstride = (size_t)KT * ld * 2;
-    auto issue = [&](int t, int buf) __attribute__((always_inline)) {
-        char* dst = smem + buf * STAGE1 + wave * 1024;
-        const size_t o = t * tstride;
-        // keys past the image's end are read as its last key (their scores are masked below)
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            dma16(kbase + o + (size_t)(min(t * KT + krow[i], N - 1) - t * KT) * (size_t)(ld * 2) + kch[i], dst + i * 4096);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            dma16(vbase + o + (size_t)(min(t * KT + vrow[i], N - 1) - t * KT) * (size_t)(ld * 2) + vch, dst + PLANE + i * 4096);
-    };
-
-    // ---- fragment addresses, as attn_fwd16_m16_kernel
-    const int k_off = pi16_row(c16, 0) * 128 + ((g4 ^ rm16_swizzle(pi16_row(c16, 0))) * 16);
-    const unsigned v_lds = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem) + PLANE + km16_read_lane_off(lane);
-
-    f32x4 oM[4][2];                          // [dt][ct]
-#pragma unroll
-    for (int d = 0; d < 4; ++d)
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) oM[d][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-    float m_run[2] = {-INFINITY, -INFINITY}, l_run[2] = {0.f, 0.f};      // l_run: this lane's share of the row sum
-
-    const int nkt = (N + KT - 1) / KT;
-    issue(0, 0);
-    for (int t = 0; t < nkt; ++t) {
-        // the wait is written out on every path, idle waves included: see attn_fwd16_kernel
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (t + 1 < nkt) issue(t + 1, (t + 1) & 1);
-        if (!wave_active) continue;
-        const char* st = smem + (t & 1) * STAGE1;
-
-        // ---- S^T = K_hi Q_hi^T in four steps (G, ks); fragment reads one step ahead
-        f32x4 sM[2][2][2];                   // [G][j][ct]
-        const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
-        h8 kh[2][2];                         // [set][j]
-        auto k_read = [&](const int step, h8(&fh)[2]) __attribute__((always_inline)) {
-            const int a = (k_off ^ ((step & 1) * 64)) + (step >> 1) * 4096;
-#pragma unroll
-            for (int j = 0; j < 2; ++j) fh[j] = *reinterpret_cast<const h8*>(st + a + j * 512);
-        };
-        k_read(0, kh[0]);
-#pragma unroll
-        for (int step = 0; step < 4; ++step) {
-            const int cur = step & 1, G = step >> 1, ks = step & 1;
-            if (step + 1 < 4) k_read(step + 1, kh[cur ^ 1]);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < 2; ++j)
-#pragma unroll
-                for (int ct = 0; ct < 2; ++ct) sM[G][j][ct] = MFMA_16x16x32(kh[cur][j], qh[ct][ks], ks == 0 ? zero4 : sM[G][j][ct]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // the first V^T fragments are fetched now: their LDS latency hides under the softmax arithmetic.  A PV step is (key step S,
-        // d tile pair dh): 4 reads = d tile x half, 4 MFMAs
-        h4 vf[2][4];                         // [set][(d tile of the pair) * 2 + half]
-        const unsigned v_st = v_lds + (t & 1) * STAGE1;
-        auto v_read = [&](auto hc, h4(&f)[4]) __attribute__((always_inline)) {
-            constexpr int HS = decltype(hc)::value, S = HS >> 1, DH = HS & 1;
-            static_for<4>([&](auto ic) __attribute__((always_inline)) {
-                constexpr int i = decltype(ic)::value, dd = i >> 1, jj = i & 1;
-                f[i] = km_tr_read<((S * 2 + jj) * 4 + 2 * DH + dd) * 512>(v_st);
-            });
-        };
-        v_read(std::integral_constant<int, 0>{}, vf[0]);
-        // ---- online softmax: the arithmetic of attn_fwd16_m16_kernel without the cross terms
-        const float c1 = scale * 1.4426950408889634f;
-        if (t == nkt - 1) {            // block-uniform: keys >= N exist in the last tile only
-            const int kbase_t = t * KT + 8 * g4;
-#pragma unroll
-            for (int G = 0; G < 2; ++G)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i)
-                        if (kbase_t + 32 * G + 4 * j + i >= N) { sM[G][j][0][i] = -INFINITY; sM[G][j][1][i] = -INFINITY; }
-        }
-        float mxp[2];
-        bool want = false;
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            float mx = -INFINITY;
-#pragma unroll
-            for (int G = 0; G < 2; ++G)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) mx = fmaxf(mx, sM[G][j][ct][i]);
-            mxp[ct] = mx * c1;                                               // c1 > 0
-            want = want || (fmaxf(m_run[ct], mxp[ct]) - m_run[ct] > 8.f);    // -inf start: inf > 8; all masked so far: NaN > 8 is false
-        }
-        const bool move = __builtin_amdgcn_ballot_w64(want) != 0;
-        if (move) {
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                float mx = mxp[ct];
-                mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-                const float m2 = fmaxf(m_run[ct], mx);
-                const float alpha = __builtin_amdgcn_exp2f(m_run[ct] - (m2 == -INFINITY ? 0.f : m2));
-                m_run[ct] = m2;
-                l_run[ct] *= alpha;
-#pragma unroll
-                for (int d = 0; d < 4; ++d) oM[d][ct] *= alpha;
-            }
-        }
-        h8 ph[2][2];                         // [key step G][ct]
-#pragma unroll
-        for (int ct = 0; ct < 2; ++ct) {
-            const float m_new = m_run[ct] == -INFINITY ? 0.f : m_run[ct];      // the guard of attn_fwd16_kernel
-            f32x2 psum2 = {0.f, 0.f};
-#pragma unroll
-            for (int G = 0; G < 2; ++G)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-#pragma unroll
-                    for (int i = 0; i < 4; i += 2) {
-                        const f32x2 m2 = {sM[G][j][ct][i], sM[G][j][ct][i + 1]};
-                        const f32x2 v2 = __builtin_elementwise_fma(m2, f32x2{c1, c1}, f32x2{-m_new, -m_new});
-                        const f32x2 p2 = {__builtin_amdgcn_exp2f(v2[0]), __builtin_amdgcn_exp2f(v2[1])};
-                        psum2 += p2;
-                        const h2v hh = __builtin_convertvector(p2, h2v);       // one packed convert, round to nearest even
-                        ph[G][ct][4 * j + i] = hh[0];
-                        ph[G][ct][4 * j + i + 1] = hh[1];
-                    }
-            l_run[ct] += psum2[0] + psum2[1];
-        }
-        // ---- O^T += V_hi^T P^T, same read-ahead
-        static_for<4>([&](auto hc) __attribute__((always_inline)) {
-            constexpr int hs = decltype(hc)::value, cur = hs & 1, S = hs >> 1, d0 = 2 * (hs & 1);
-            if constexpr (hs + 1 < 4) {
-                v_read(std::integral_constant<int, hs + 1>{}, vf[cur ^ 1]);
-                asm volatile("s_waitcnt lgkmcnt(4)" ::: "memory");       // LDS returns in order: the 4 reads of step hs have landed
-            } else {
-                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            const h4(&f)[4] = vf[cur];
-            const h8 vh0 = __builtin_shufflevector(f[0], f[1], 0, 1, 2, 3, 4, 5, 6, 7), vh1 = __builtin_shufflevector(f[2], f[3], 0, 1, 2, 3, 4, 5, 6, 7);
-            oM[d0][0] = MFMA_16x16x32(vh0, ph[S][0], oM[d0][0]);
-            oM[d0][1] = MFMA_16x16x32(vh0, ph[S][1], oM[d0][1]);
-            oM[d0 + 1][0] = MFMA_16x16x32(vh1, ph[S][0], oM[d0 + 1][0]);
-            oM[d0 + 1][1] = MFMA_16x16x32(vh1, ph[S][1], oM[d0 + 1][1]);
-            __builtin_amdgcn_sched_barrier(0);
-        });
-    }
-    if (!wave_active) return;
-    if (b >= B_f32) out = nullptr;
-#pragma unroll
-    for (int ct = 0; ct < 2; ++ct) {
-        float l_tot = l_run[ct];                      // the row sum over the query's four lanes, once
-        l_tot += __shfl_xor(l_tot, 16, 64);
-        l_tot += __shfl_xor(l_tot, 32, 64);
-        const float inv = 1.f / l_tot;
-        const int qrow = q0 + 16 * ct + c16;
-        if (qrow < N) {
-            const size_t ro = ((size_t)b * N + qrow) * D + h * HD;
-#pragma unroll
-            for (int d = 0; d < 4; ++d) {             // a query's four lanes write 64 contiguous bytes (fp32) per instruction
-                float v[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) v[j] = oM[d][ct][j] * inv;
-                const int col = 16 * d + 4 * g4;
-                if (out) *reinterpret_cast<float4*>(out + ro + col) = make_float4(v[0], v[1], v[2], v[3]);
-                if (out_hi) {
-                    __half hh[4], ll[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        if (out_scale > 0.f) split_f32_u(v[j] * out_scale, hh[j], ll[j]);
-                        else split_f32(v[j], hh[j], ll[j]);
-                    }
-                    *reinterpret_cast<uint2*>(out_hi + ro + col) = *reinterpret_cast<const uint2*>(hh);
-                    *reinterpret_cast<uint2*>(out_lo + ro + col) = *reinterpret_cast<const uint2*>(ll);
-                }
-            }
-        }
-    }
-}
-
 
 }  // namespace
 
@@ -917,7 +711,7 @@ static int attn_fwd16_launch(const void* qkv_hi, const void* qkv_lo, void* out_h
                              int32_t H, int32_t hd, float scale, int32_t out_exp, int32_t mfma, int32_t products, dupl_stream_t s) {
     if (mfma != 0 && mfma != 16 && mfma != 32) return DUPL_ERR_ARG;
     if (products != 1 && products != 3) return DUPL_ERR_ARG;
-    const bool single = products == 1;       // attn_fwd16_h1_kernel: the hi plane only, the 16x16x32 shape only, no lse
+    const bool single = products == 1;       // attn_fwd16_m16_kernel<1>: the hi plane only, the 16x16x32 shape only, no lse
     if (single && mfma == 32) return DUPL_ERR_ARG;
     if (single && !qkv_lo) qkv_lo = qkv_hi;  // (not read; stands in for the checks below)
     if (out_exp < 0 || out_exp > 15 || !sv || n < 1 || n > DUPL_ATTN_SEGS_MAX) return DUPL_ERR_ARG;
@@ -948,15 +742,16 @@ static int attn_fwd16_launch(const void* qkv_hi, const void* qkv_lo, void* out_h
     // the last bits, and an image's rows must not depend on the launch it rides in (a segmented launch against one launch per batch,
     // 8 images against the same images two at a time) -- so one kernel serves all lengths.
     const bool m16 = mfma != 32;
-    if (single)
-        DUPL_LAUNCH(attn_fwd16_h1_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)s, (const __half*)qkv_hi, (__half*)out_hi,
-                    (__half*)out_lo, g, H, scale, g_attn16_remap, out_exp ? ldexpf(1.f, out_exp) : 0.f);
-    else if (m16)
-        DUPL_LAUNCH(attn_fwd16_m16_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)s, (const __half*)qkv_hi, (const __half*)qkv_lo,
-                    (__half*)out_hi, (__half*)out_lo, g, H, scale, g_attn16_remap, out_exp ? ldexpf(1.f, out_exp) : 0.f);
-    else
+    const float out_scale = out_exp ? ldexpf(1.f, out_exp) : 0.f;
+    if (!m16)
         DUPL_LAUNCH(attn_fwd16_kernel, dim3((unsigned)total), dim3(256), 0, (hipStream_t)s, (const __half*)qkv_hi, (const __half*)qkv_lo,
-                    (__half*)out_hi, (__half*)out_lo, g, H, scale, g_attn16_remap, out_exp ? ldexpf(1.f, out_exp) : 0.f);
+                    (__half*)out_hi, (__half*)out_lo, g, H, scale, g_attn16_remap, out_scale);
+    else if (!single)
+        DUPL_LAUNCH(attn_fwd16_m16_kernel<3>, dim3((unsigned)total), dim3(256), 0, (hipStream_t)s, (const __half*)qkv_hi, (const __half*)qkv_lo,
+                    (__half*)out_hi, (__half*)out_lo, g, H, scale, g_attn16_remap, out_scale);
+    else
+        DUPL_LAUNCH(attn_fwd16_m16_kernel<1>, dim3((unsigned)total), dim3(256), 0, (hipStream_t)s, (const __half*)qkv_hi, (const __half*)qkv_lo,
+                    (__half*)out_hi, (__half*)out_lo, g, H, scale, g_attn16_remap, out_scale);
     return dupl_launch_status();
 }
 

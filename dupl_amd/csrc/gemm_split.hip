@@ -968,14 +968,29 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring_kernel(co
 //     phase can refill the B fragments in place, block by block.  Phase i < WM - 1 reads A(i + 1) under the MFMAs of A(i); then ONE
 //     counted s_waitcnt vmcnt + raw s_barrier (tile t + 1 landed, every wave done reading tile t); the last phase reads A(0) and B of
 //     tile t + 1 and issues the DMA of tile t + STAGES into tile t's stage.
-template <int WM, int WN, int NWM, int NWN, int WPS, int STAGES>
+//
+// NP = 1 is the single-product forward (dupl_gemm16_desc.products = 1, the opt-in "f16" mode of the no-grad encoder passes):
+//     C = act(alpha * post_scale * A_hi . B_hi^T + bias) (+ res),   fp32 accumulation
+// ONE MFMA per 16 x 16 block and k-tile instead of three, and only the hi planes are fetched (the lo pointers are never read and may
+// be NULL); the planes are the ones the f16x3 forward takes, in either format -- the format only decides post_scale.  The result
+// differs from the exact product by the rounding of the operands to fp16 (relative 2^-11 per element).  What NP changes, all of it
+// behind PL (planes per operand) below:
+//   * a k-tile is PL (PA + PB) pieces.  With one plane that is half a stage's bytes (32 KB at 256 x 256, 24 KB at 256 x 128), and the
+//     LDS goes to a deeper ring instead (the launcher's G16H_STAGES): the loop has a third of the MFMA cycles per barrier to hide a
+//     DMA round trip under.  The k-tile stays ONE MFMA k-step (32), so K % 32 == 0 is all a shape needs.
+//   * a phase is 2 NP CB MFMAs with 2 PL fragment reads under its first PL column blocks.
+//   * NP = 1 alone flushes the epilogue's amax (p.amax_out).
+template <int WM, int WN, int NWM, int NWN, int WPS, int STAGES, int NP = 3>
 __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(const dupl_gemm16_desc p, const int g_gm) {
     using G = RingGeom<WM, WN, NWM, NWN>;
-    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB, STAGE = G::STAGE, PPW = G::PPW;
+    static_assert(NP == 1 || NP == 3, "one product or the three of f16x3");
+    constexpr int PL = NP == 3 ? 2 : 1;              // planes per operand: hi, lo
+    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB;
+    constexpr int STAGE = PL * (PA + PB) * 1024, PPW = PL * (PA + PB) / NW;      // A planes | B planes, piece g at g * 1024 bytes
     constexpr int RB = 2 * WM, CB = 2 * WN;          // 16 x 16 blocks of the wave tile
     constexpr int NPH = WM;                          // phases of a k-tile: two row blocks each
-    constexpr int NMF = 3 * 2 * CB;                  // MFMAs of a phase
-    static_assert(STAGES * STAGE <= 160 * 1024, "LDS");
+    static_assert(PL * (PA + PB) % NW == 0, "pieces must divide over the waves");
+    static_assert(STAGES >= 2 && STAGES * STAGE <= 160 * 1024, "LDS");
     static_assert((STAGES - 1) * PPW <= 63, "vmcnt range");
     static_assert(NPH % 2 == 0, "the A fragment sets alternate by phase");
     __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE];
@@ -998,7 +1013,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
     const int m0 = tm * BM, n0 = tn * BN;
     const int nt = p.K / TBK;
 
-    // ---- DMA plan (as gemm_f16x3_ring_kernel, with this kernel's swizzle): piece g = wave + NW * i
+    // ---- DMA plan (as gemm_f16x3_ring_kernel, with this kernel's swizzle): piece g = wave + NW * i; rows past the operand's end are
+    // read as its last row (their results are never stored)
     const int prow = lane >> 2;
     const int jsrc = (lane & 3) ^ ((4 - (prow >> 2)) & 3);
     const char* gp[PPW];
@@ -1008,8 +1024,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
         const __half* plane;
         int ld, r0, R, q;
         if (g < PA) { plane = static_cast<const __half*>(p.A_hi); ld = p.lda; r0 = m0; R = p.M; q = g; }
-        else if (g < 2 * PA) { plane = static_cast<const __half*>(p.A_lo); ld = p.lda; r0 = m0; R = p.M; q = g - PA; }
-        else if (g < 2 * PA + PB) { plane = static_cast<const __half*>(p.B_hi); ld = p.ldb; r0 = n0; R = p.N; q = g - 2 * PA; }
+        else if (PL == 2 && g < 2 * PA) { plane = static_cast<const __half*>(p.A_lo); ld = p.lda; r0 = m0; R = p.M; q = g - PA; }
+        else if (PL == 1 || g < 2 * PA + PB) { plane = static_cast<const __half*>(p.B_hi); ld = p.ldb; r0 = n0; R = p.N; q = g - PL * PA; }
         else { plane = static_cast<const __half*>(p.B_lo); ld = p.ldb; r0 = n0; R = p.N; q = g - 2 * PA - PB; }
         const int row = min(r0 + q * 16 + prow, R - 1);
         gp[i] = reinterpret_cast<const char*>(plane + (size_t)row * ld) + jsrc * 16;
@@ -1025,65 +1041,70 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
     // ---- fragment addresses (bytes inside a stage): plane base + row * 64 + ((lane >> 4) ^ swizzle(row)) * 16
     const int l15 = lane & 15;
     const int ch = ((lane >> 4) ^ ((4 - (l15 >> 2)) & 3)) * 16;
-    const int a_off = (wm * (32 * WM) + l15) * 64 + ch, b_off = 2 * PA * 1024 + (wn * (32 * WN) + l15) * 64 + ch;
+    const int a_off = (wm * (32 * WM) + l15) * 64 + ch, b_off = PL * PA * 1024 + (wn * (32 * WN) + l15) * 64 + ch;
 
     f32x4 acc[RB][CB];
 #pragma unroll
     for (int i = 0; i < RB; ++i)
 #pragma unroll
         for (int j = 0; j < CB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // A: two sets of {hi rb 0, hi rb 1, lo rb 0, lo rb 1}, alternating by phase; B: {hi cb .., lo cb ..} of the k-tile
-    h8 fa0[4], fa1[4], fb[2 * CB];
-    auto read_a = [&](auto rc, const char* st, const int ph, h8(&fa)[4]) __attribute__((always_inline)) {
+    // A: two sets of {hi rb 0, hi rb 1, lo rb 0, lo rb 1}, alternating by phase; B: {hi cb .., lo cb ..} of the k-tile (PL = 1: no lo)
+    h8 fa0[2 * PL], fa1[2 * PL], fb[PL * CB];
+    auto read_a = [&](auto rc, const char* st, const int ph, h8(&fa)[2 * PL]) __attribute__((always_inline)) {
         constexpr int R = decltype(rc)::value;
         fa[R] = *reinterpret_cast<const h8*>(st + (R >> 1) * (PA * 1024) + a_off + (2 * ph + (R & 1)) * 1024);
     };
     auto read_b = [&](auto jc, const char* st) __attribute__((always_inline)) {
         constexpr int J = decltype(jc)::value;
         fb[J] = *reinterpret_cast<const h8*>(st + b_off + J * 1024);
-        fb[CB + J] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_off + J * 1024);
+        if constexpr (PL == 2) fb[CB + J] = *reinterpret_cast<const h8*>(st + PB * 1024 + b_off + J * 1024);
     };
-    // column block J of a phase: hi.hi, hi.lo, lo.hi on each of its two accumulators
-    auto mfma6 = [&](auto phc, auto jc, const h8(&fa)[4]) __attribute__((always_inline)) {
+    // column block J of a phase: hi.hi (NP = 3: then hi.lo, lo.hi) on each of its two accumulators
+    constexpr int NMB = 2 * NP;                      // MFMAs of a column block
+    auto mfma_block = [&](auto phc, auto jc, const h8(&fa)[2 * PL]) __attribute__((always_inline)) {
         constexpr int PH = decltype(phc)::value, J = decltype(jc)::value;
 #pragma unroll
         for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[k], fb[J], acc[2 * PH + k][J], 0, 0, 0);
+        if constexpr (NP == 3) {
 #pragma unroll
-        for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[k], fb[CB + J], acc[2 * PH + k][J], 0, 0, 0);
+            for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[k], fb[CB + J], acc[2 * PH + k][J], 0, 0, 0);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[2 + k], fb[J], acc[2 * PH + k][J], 0, 0, 0);
+            for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[2 + k], fb[J], acc[2 * PH + k][J], 0, 0, 0);
+        }
     };
     constexpr int S_MFMA = 0x008, S_DSR = 0x100, S_VMEM = 0x010;
-    // issue-order hint for one column block (6 MFMAs) with NRD fragment reads under it: one read behind each of the first MFMAs
-    auto hint6 = [](auto nrd) __attribute__((always_inline)) {
-        constexpr int NRD = decltype(nrd)::value;
-        static_for<NRD>([](auto) __attribute__((always_inline)) {
+    // issue-order hint for one column block (NMB MFMAs) with NRD fragment reads under it: one read behind each of the first MFMAs,
+    // whatever is left of them behind the last one
+    auto hint = [](auto nrd) __attribute__((always_inline)) {
+        constexpr int NRD = decltype(nrd)::value, PAIRS = NRD < NMB ? NRD : NMB - 1;
+        static_for<PAIRS>([](auto) __attribute__((always_inline)) {
             __builtin_amdgcn_sched_group_barrier(S_MFMA, 1, 0);
             __builtin_amdgcn_sched_group_barrier(S_DSR, 1, 0);
         });
-        __builtin_amdgcn_sched_group_barrier(S_MFMA, 6 - NRD, 0);
+        __builtin_amdgcn_sched_group_barrier(S_MFMA, NMB - PAIRS, 0);
+        if constexpr (NRD > PAIRS) __builtin_amdgcn_sched_group_barrier(S_DSR, NRD - PAIRS, 0);
     };
-    // phases 0 .. NPH - 2 of the tile in stage st: the first two column blocks of phase i run over the reads of A(i + 1); the very
-    // first one also over the tile's own last B pair (its registers are busy to the end of the previous tile's last phase)
+    // phases 0 .. NPH - 2 of the tile in stage st: the first PL column blocks of phase i run over the reads of A(i + 1); the very
+    // first one also over the tile's own last B fragments (their registers are busy to the end of the previous tile's last phase)
     auto inner_phases = [&](const char* st) __attribute__((always_inline)) {
         static_for<NPH - 1>([&](auto ph) __attribute__((always_inline)) {
             constexpr int PH = decltype(ph)::value;
             static_for<CB>([&](auto j) __attribute__((always_inline)) {
                 constexpr int J = decltype(j)::value;
-                constexpr int NRD = (J < 2 ? 2 : 0) + (PH == 0 && J == 0 ? 2 : 0);
+                constexpr int NRD = (J < PL ? 2 : 0) + (PH == 0 && J == 0 ? PL : 0);
                 if constexpr (PH == 0 && J == 0) read_b(std::integral_constant<int, CB - 1>{}, st);
-                if constexpr (J < 2) {
+                if constexpr (J < PL) {
                     read_a(std::integral_constant<int, 2 * J>{}, st, PH + 1, PH & 1 ? fa0 : fa1);
                     read_a(std::integral_constant<int, 2 * J + 1>{}, st, PH + 1, PH & 1 ? fa0 : fa1);
                 }
-                mfma6(ph, j, PH & 1 ? fa1 : fa0);
-                hint6(std::integral_constant<int, NRD>{});
+                mfma_block(ph, j, PH & 1 ? fa1 : fa0);
+                hint(std::integral_constant<int, NRD>{});
             });
         });
     };
-    // the last phase.  LOAD: the fragments of the next tile (stage nx) are read under it -- A(0) under column block 0, the B pair of
-    // column block j IN PLACE under block j + 1, once the MFMAs of block j are out (the last pair: inner_phases); DMA: the PPW pieces of
-    // tile t + STAGES go out between the blocks.  The loads stand in the source in the order the hints pin them (an LDS read and an
+    // the last phase.  LOAD: the fragments of the next tile (stage nx) are read under it -- A(0) under column block 0, the B fragments
+    // of column block j IN PLACE under block j + 1, once the MFMAs of block j are out (the last ones: inner_phases); DMA: the PPW pieces
+    // of tile t + STAGES go out between the blocks.  The loads stand in the source in the order the hints pin them (an LDS read and an
     // LDS-DMA write are ordered for the compiler).
     auto last_phase = [&](auto loadc, auto dmac, const char* nx, char* dst) __attribute__((always_inline)) {
         constexpr bool LOAD = decltype(loadc)::value, DMA = decltype(dmac)::value;
@@ -1092,14 +1113,14 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
             constexpr int J = decltype(j)::value;
             constexpr int D0 = J * PPW / CB, D1 = (J + 1) * PPW / CB;      // this block's DMA pieces
             if constexpr (LOAD) {
-                if constexpr (J == 0) static_for<4>([&](auto r) __attribute__((always_inline)) { read_a(r, nx, 0, fa0); });
+                if constexpr (J == 0) static_for<2 * PL>([&](auto r) __attribute__((always_inline)) { read_a(r, nx, 0, fa0); });
                 else read_b(std::integral_constant<int, J - 1>{}, nx);
             }
             if constexpr (DMA) static_for<D1 - D0>([&](auto i) __attribute__((always_inline)) {
                 dma_item(std::integral_constant<int, D0 + decltype(i)::value>{}, dst);
             });
-            mfma6(ph, j, fa1);
-            hint6(std::integral_constant<int, LOAD ? (J == 0 ? 4 : 2) : 0>{});
+            mfma_block(ph, j, fa1);
+            hint(std::integral_constant<int, LOAD ? (J == 0 ? 2 * PL : PL) : 0>{});
             if constexpr (DMA && D1 > D0) __builtin_amdgcn_sched_group_barrier(S_VMEM, D1 - D0, 0);
         });
     };
@@ -1113,7 +1134,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    static_for<4>([&](auto r) __attribute__((always_inline)) { read_a(r, smem, 0, fa0); });
+    static_for<2 * PL>([&](auto r) __attribute__((always_inline)) { read_a(r, smem, 0, fa0); });
     static_for<CB - 1>([&](auto j) __attribute__((always_inline)) { read_b(j, smem); });
     int rb = 0;
     int t = 0;
@@ -1144,193 +1165,14 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-    constexpr int RBP = (NW * (16 * RB) * (16 * CB) * 4 <= STAGES * STAGE) ? RB : RB / 2;   // row blocks per epilogue pass
-    static_assert(NW * (16 * RBP) * (16 * CB) * 4 <= STAGES * STAGE, "epilogue tiles must fit the stages");
-    float amx = 0.f;
-    gemm16_epilogue_lds16<RB, CB, RBP>(p, acc, reinterpret_cast<float*>(smem) + wave * ((16 * RBP) * (16 * CB)), m0 + wm * (32 * WM),
-                                       n0 + wn * (32 * WN), lane, 1, amx);
-}
-
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// The single-product forward kernel (dupl_gemm16_desc.products = 1, the opt-in "f16" mode of the no-grad encoder passes):
-//     C = act(alpha * post_scale * A_hi . B_hi^T + bias) (+ res),   fp32 accumulation
-// ONE v_mfma_f32_16x16x32_f16 per 16 x 16 block and k-tile instead of three, and only the hi planes are fetched (the lo pointers are
-// never read and may be NULL); the planes are the ones the f16x3 forward takes, in either format -- the format only decides
-// post_scale.  The result differs from the exact product by the rounding of the operands to fp16 (relative 2^-11 per element).
-// gemm_f16x3_ring16_kernel is the model: block and wave tiles, tile order, piece DMA, swizzle, the counted vmcnt + raw barrier
-// pipeline, the phases (A fragments of two row blocks double-buffered, B fragments held through the k-tile and refilled in place in
-// the last phase) and the epilogue are its own.  What changes with one plane per operand:
-//   * a k-tile is PA + PB pieces (A_hi | B_hi), half a stage's bytes: 32 KB at 256 x 256, 24 KB at 256 x 128.  The k-tile stays ONE
-//     MFMA k-step (32), so K % 32 == 0 is all a shape needs, and the LDS goes to a deeper ring instead (STAGES template argument,
-//     the launcher's G16H_STAGES): the loop has a third of the MFMA cycles per barrier to hide a DMA round trip under.
-//   * a phase is 2 CB MFMAs (8: 128 cycles) with 2 fragment reads under its first column block.
-template <int WM, int WN, int NWM, int NWN, int WPS, int STAGES>
-__global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16_ring16_kernel(const dupl_gemm16_desc p, const int g_gm) {
-    using G = RingGeom<WM, WN, NWM, NWN>;
-    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB;
-    constexpr int NP = PA + PB, STAGE = NP * 1024, PPW = NP / NW;      // hi planes only
-    constexpr int RB = 2 * WM, CB = 2 * WN;          // 16 x 16 blocks of the wave tile
-    constexpr int NPH = WM;                          // phases of a k-tile: two row blocks each
-    static_assert(NP % NW == 0, "pieces must divide over the waves");
-    static_assert(STAGES >= 2 && STAGES * STAGE <= 160 * 1024, "LDS");
-    static_assert((STAGES - 1) * PPW <= 63, "vmcnt range");
-    static_assert(NPH % 2 == 0, "the A fragment sets alternate by phase");
-    __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE];
-    const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wm = wave / NWN, wn = wave % NWN;
-
-    int m0, n0;
-    const TileOrder<BM, BN> order((p.M + BM - 1) / BM, (p.N + BN - 1) / BN, g_gm);
-    order.tile_origin(blockIdx.x, m0, n0);
-    const int nt = p.K / TBK;
-
-    // ---- DMA plan: piece g = wave + NW * i; pieces [0, PA) are A_hi, [PA, NP) B_hi; rows past the operand's end are read as its
-    // last row (their results are never stored)
-    const int prow = lane >> 2;
-    const int jsrc = (lane & 3) ^ ((4 - (prow >> 2)) & 3);
-    const char* gp[PPW];
-#pragma unroll
-    for (int i = 0; i < PPW; ++i) {
-        const int g = wave + NW * i;
-        const bool isa = g < PA;
-        const __half* plane = static_cast<const __half*>(isa ? p.A_hi : p.B_hi);
-        const int ld = isa ? p.lda : p.ldb, R = isa ? p.M : p.N;
-        const int row = min((isa ? m0 + g * 16 : n0 + (g - PA) * 16) + prow, R - 1);
-        gp[i] = reinterpret_cast<const char*>(plane + (size_t)row * ld) + jsrc * 16;
-    }
-    auto dma_item = [&](auto dc, char* dst) __attribute__((always_inline)) {
-        constexpr int I = decltype(dc)::value;
-        g16_dma_piece(gp[I], dst + I * (NW * 1024));
-    };
-    auto issue = [&](int buf) __attribute__((always_inline)) {   // next k-tile of this block -> stage buf
-        static_for<PPW>([&](auto i) __attribute__((always_inline)) { dma_item(i, smem + buf * STAGE + wave * 1024); });
-    };
-
-    // ---- fragment addresses (bytes inside a stage): plane base + row * 64 + ((lane >> 4) ^ swizzle(row)) * 16
-    const int l15 = lane & 15;
-    const int ch = ((lane >> 4) ^ ((4 - (l15 >> 2)) & 3)) * 16;
-    const int a_off = (wm * (32 * WM) + l15) * 64 + ch, b_off = PA * 1024 + (wn * (32 * WN) + l15) * 64 + ch;
-
-    f32x4 acc[RB][CB];
-#pragma unroll
-    for (int i = 0; i < RB; ++i)
-#pragma unroll
-        for (int j = 0; j < CB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // A: two sets of {row block 0, row block 1} of a phase, alternating by phase; B: the CB column blocks of the k-tile
-    h8 fa0[2], fa1[2], fb[CB];
-    auto read_a = [&](auto rc, const char* st, const int ph, h8(&fa)[2]) __attribute__((always_inline)) {
-        constexpr int R = decltype(rc)::value;
-        fa[R] = *reinterpret_cast<const h8*>(st + a_off + (2 * ph + R) * 1024);
-    };
-    auto read_b = [&](auto jc, const char* st) __attribute__((always_inline)) {
-        constexpr int J = decltype(jc)::value;
-        fb[J] = *reinterpret_cast<const h8*>(st + b_off + J * 1024);
-    };
-    // column block J of a phase: one product on each of its two accumulators
-    auto mfma2 = [&](auto phc, auto jc, const h8(&fa)[2]) __attribute__((always_inline)) {
-        constexpr int PH = decltype(phc)::value, J = decltype(jc)::value;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(fa[k], fb[J], acc[2 * PH + k][J], 0, 0, 0);
-    };
-    constexpr int S_MFMA = 0x008, S_DSR = 0x100, S_VMEM = 0x010;
-    // issue-order hint for one column block (2 MFMAs) with NRD fragment reads under it, spread behind the MFMAs
-    auto hint2 = [](auto nrd) __attribute__((always_inline)) {
-        constexpr int NRD = decltype(nrd)::value;
-        static_for<2>([](auto ic) __attribute__((always_inline)) {
-            constexpr int I = decltype(ic)::value, n = (I + 1) * NRD / 2 - I * NRD / 2;
-            __builtin_amdgcn_sched_group_barrier(S_MFMA, 1, 0);
-            if constexpr (n > 0) __builtin_amdgcn_sched_group_barrier(S_DSR, n, 0);
-        });
-    };
-    // phases 0 .. NPH - 2 of the tile in stage st: column block 0 of phase i runs over the reads of A(i + 1); the very first one also
-    // over the tile's own last B fragment (its register is busy to the end of the previous tile's last phase)
-    auto inner_phases = [&](const char* st) __attribute__((always_inline)) {
-        static_for<NPH - 1>([&](auto ph) __attribute__((always_inline)) {
-            constexpr int PH = decltype(ph)::value;
-            static_for<CB>([&](auto j) __attribute__((always_inline)) {
-                constexpr int J = decltype(j)::value;
-                constexpr int NRD = (J == 0 ? 2 : 0) + (PH == 0 && J == 0 ? 1 : 0);
-                if constexpr (PH == 0 && J == 0) read_b(std::integral_constant<int, CB - 1>{}, st);
-                if constexpr (J == 0) {
-                    read_a(std::integral_constant<int, 0>{}, st, PH + 1, PH & 1 ? fa0 : fa1);
-                    read_a(std::integral_constant<int, 1>{}, st, PH + 1, PH & 1 ? fa0 : fa1);
-                }
-                mfma2(ph, j, PH & 1 ? fa1 : fa0);
-                hint2(std::integral_constant<int, NRD>{});
-            });
-        });
-    };
-    // the last phase.  LOAD: the fragments of the next tile (stage nx) are read under it -- A(0) under column block 0, the B fragment
-    // of column block j IN PLACE under block j + 1 (the last one: inner_phases); DMA: the PPW pieces of tile t + STAGES go out between
-    // the blocks.  The loads stand in the source in the order the hints pin them.
-    auto last_phase = [&](auto loadc, auto dmac, const char* nx, char* dst) __attribute__((always_inline)) {
-        constexpr bool LOAD = decltype(loadc)::value, DMA = decltype(dmac)::value;
-        constexpr auto ph = std::integral_constant<int, NPH - 1>{};
-        static_for<CB>([&](auto j) __attribute__((always_inline)) {
-            constexpr int J = decltype(j)::value;
-            constexpr int D0 = J * PPW / CB, D1 = (J + 1) * PPW / CB;      // this block's DMA pieces
-            if constexpr (LOAD) {
-                if constexpr (J == 0) static_for<2>([&](auto r) __attribute__((always_inline)) { read_a(r, nx, 0, fa0); });
-                else read_b(std::integral_constant<int, J - 1>{}, nx);
-            }
-            if constexpr (DMA) static_for<D1 - D0>([&](auto i) __attribute__((always_inline)) {
-                dma_item(std::integral_constant<int, D0 + decltype(i)::value>{}, dst);
-            });
-            mfma2(ph, j, fa1);
-            hint2(std::integral_constant<int, LOAD ? (J == 0 ? 2 : 1) : 0>{});
-            if constexpr (DMA && D1 > D0) __builtin_amdgcn_sched_group_barrier(S_VMEM, D1 - D0, 0);
-        });
-    };
-    // ---- pipeline, as gemm_f16x3_ring16_kernel.  Tile t lives in stage t % STAGES.  Iteration t: the inner phases; lgkmcnt(0),
-    // vmcnt((STAGES - 2) PPW): my pieces of tile t + 1 landed; s_barrier: every wave is done reading tile t; the last phase, which
-    // sends the DMA of tile t + STAGES into tile t's stage.  The last STAGES iterations run without DMA.
-#pragma unroll
-    for (int s = 0; s < STAGES; ++s)
-        if (s < nt) issue(s);
-    if (nt >= STAGES) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 1) * PPW) : "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    static_for<2>([&](auto r) __attribute__((always_inline)) { read_a(r, smem, 0, fa0); });
-    static_for<CB - 1>([&](auto j) __attribute__((always_inline)) { read_b(j, smem); });
-    int rb = 0;
-    int t = 0;
-    for (; t + STAGES < nt; ++t) {
-        const int nb = rb + 1 == STAGES ? 0 : rb + 1;
-        inner_phases(smem + rb * STAGE);
-        __builtin_amdgcn_sched_barrier(0);      // the MFMAs of the inner phases stay in front of the wait
-        __builtin_amdgcn_s_waitcnt(WAIT_LGKM0_VM((STAGES - 2) * PPW));
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        last_phase(std::true_type{}, std::true_type{}, smem + nb * STAGE, smem + rb * STAGE + wave * 1024);
-        rb = nb;
-    }
-    for (; t + 1 < nt; ++t) {
-        const int nb = rb + 1 == STAGES ? 0 : rb + 1;
-        inner_phases(smem + rb * STAGE);
-        __builtin_amdgcn_sched_barrier(0);
-        __builtin_amdgcn_s_waitcnt(WAIT_LGKM0_VM(0));
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        last_phase(std::true_type{}, std::false_type{}, smem + nb * STAGE, nullptr);
-        rb = nb;
-    }
-    inner_phases(smem + rb * STAGE);
-    last_phase(std::false_type{}, std::false_type{}, nullptr, nullptr);
-
-    // every wave is done reading the stages and no DMA is in flight -> reuse the LDS for the epilogue tiles
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
     constexpr int WTILE = NW * 16 * (16 * CB) * 4;          // bytes of one row block of every wave's tile
     constexpr int RBP = RB * WTILE <= STAGES * STAGE ? RB : ((RB / 2) * WTILE <= STAGES * STAGE ? RB / 2 : RB / 4);   // row blocks per pass
     static_assert(RBP >= 1 && RBP * WTILE <= STAGES * STAGE, "epilogue tiles must fit the stages");
     float amx = 0.f;
     gemm16_epilogue_lds16<RB, CB, RBP>(p, acc, reinterpret_cast<float*>(smem) + wave * ((16 * RBP) * (16 * CB)), m0 + wm * (32 * WM),
                                        n0 + wn * (32 * WN), lane, 1, amx);
-    if (p.amax_out) gemm16_amax_flush(static_cast<unsigned int*>(p.amax_out), amx, reinterpret_cast<float*>(smem), wave, lane, NW);
+    if constexpr (NP == 1)
+        if (p.amax_out) gemm16_amax_flush(static_cast<unsigned int*>(p.amax_out), amx, reinterpret_cast<float*>(smem), wave, lane, NW);
 }
 
 
@@ -2017,6 +1859,35 @@ constexpr int G16_TILES[] = {
     22,   // gemm_f16x3_ring16_kernel, 256 x 128; format 1 on the 16x16x32 MFMA, one block per tile
 };
 
+// The two forward tiles on the 16x16x32 MFMA (gemm_f16x3_ring16_kernel), for the format 1 f16x3 forward and the single-product forward
+// alike: 18 = 256 x 256 (`big`) where the grid fills the chip, 22 = 256 x 128 (`small`) below.  Both tiles carry the same bits.
+static int g16_tile16(const dupl_gemm16_desc& d) {
+    return ((d.M + 255) / 256) * ((d.N + 255) / 256) >= G16_F1_BIG_FROM ? 18 : 22;
+}
+using g16_kernel_t = void (*)(dupl_gemm16_desc, int);
+static void g16_launch16(const dupl_gemm16_desc& d, const int t, const bool automatic, const int group, hipStream_t s, g16_kernel_t big,
+                         g16_kernel_t small) {
+    auto launch = [&](g16_kernel_t k, const dupl_gemm16_desc& q, const int bn) {
+        DUPL_LAUNCH(k, dim3((unsigned)(((q.M + 255) / 256) * ((q.N + bn - 1) / bn))), dim3(512), 0, s, q, group);
+    };
+    if (t == 22) return launch(small, d, 128);
+    // One block per CU and launch: nb22 tiles take ceil(nb22 / 256) rounds, and a last round that holds a few tiles costs as
+    // much as a full one.  The merged ms-CAM / training pass of a step is exactly that case -- 21 976 rows = 86 row tiles, x
+    // {12, 9, 3} column tiles = 1 032 / 774 / 258 tiles = 4, 3, 1 full rounds + 8 / 6 / 2 tiles (rocprofv3, one stream: 340 us
+    // per launch where 6 280 + 15 696 rows took 290).  So: when the last round would be less than 30 % full, the rows of
+    // the full rounds go to this kernel and the remaining row tiles to the 256 x 128 kernel (rows are independent: two
+    // launches on the stream, each on its own row range of every operand).  Next to a second stream the tail is filled by
+    // the other student's blocks anyway; alone this is worth 9-22 % per launch.  The automatic choice only.
+    const int cn = (d.N + 255) / 256, rm = (d.M + 255) / 256, cus = 256;
+    const int nb22 = rm * cn, full = nb22 / cus, tail = nb22 - full * cus;
+    const int r_big = full > 0 ? (full * cus) / cn : 0;
+    dupl_gemm16_desc d1, d2;
+    if (automatic && full > 0 && tail > 0 && tail * 10 < cus * 3 && r_big > 0 && r_big < rm && !d.amax_out && g16_split_rows(d, r_big * 256, d1, d2)) {
+        launch(big, d1, 256);
+        launch(small, d2, 128);
+    } else launch(big, d, 256);
+}
+
 static int g16_launch_hi(const dupl_gemm16_desc& d, const int tile, const int group, hipStream_t s);      // (below: its kernels are emitted last)
 
 extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) {
@@ -2148,32 +2019,13 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         // every forward shape, alone and next to a second stream (15 696 x 3 072 x 768 bias + GELU -> planes: 247 vs 300 TF/s-eq,
         // 15 696 x 768 x 3 072 bias + residual: 295 vs 328; profiles/r06_tile16.txt): with one wave per SIMD nothing covers a wave's
         // own waits, the result tile 7 gave in round 3)
-        const int nb22 = ((d->M + 255) / 256) * ((d->N + 255) / 256), nb21 = ((d->M + 255) / 256) * ((d->N + 127) / 128);
+        const int nb21 = ((d->M + 255) / 256) * ((d->N + 127) / 128);
         // (18 / 22: the same two tiles on the 16x16x32 MFMA, gemm_f16x3_ring16_kernel; the launcher's own choice, since the clock the
         // chip holds under this loop is higher on that shape.  Both tiles switch together: they are bit-identical to each other)
-        int t = (g16_tile == 8 || g16_tile == 12 || g16_tile == 14 || g16_tile == 18 || g16_tile == 22) ? g16_tile
-                                                                                                         : (nb22 >= G16_F1_BIG_FROM ? 18 : 22);
+        int t = (g16_tile == 8 || g16_tile == 12 || g16_tile == 14 || g16_tile == 18 || g16_tile == 22) ? g16_tile : g16_tile16(*d);
         if (d->K / TBK < 3 && t == 14) t = 12;
-        if (t == 18) {
-            // One block per CU and launch: nb22 tiles take ceil(nb22 / 256) rounds, and a last round that holds a few tiles costs as
-            // much as a full one.  The merged ms-CAM / training pass of a step is exactly that case -- 21 976 rows = 86 row tiles, x
-            // {12, 9, 3} column tiles = 1 032 / 774 / 258 tiles = 4, 3, 1 full rounds + 8 / 6 / 2 tiles (rocprofv3, one stream: 340 us
-            // per launch where 6 280 + 15 696 rows took 290).  So: when the last round would be less than 30 % full, the rows of
-            // the full rounds go to this kernel and the remaining row tiles to the 256 x 128 kernel (rows are independent: two
-            // launches on the stream, each on its own row range of every operand).  Next to a second stream the tail is filled by
-            // the other student's blocks anyway; alone this is worth 9-22 % per launch.  The automatic choice only.
-            const int cn = (d->N + 255) / 256, rm = (d->M + 255) / 256, cus = 256;
-            const int full = nb22 / cus, tail = nb22 - full * cus;
-            const int r_big = full > 0 ? (full * cus) / cn : 0;
-            dupl_gemm16_desc d1, d2;
-            if (g16_tile == 0 && full > 0 && tail > 0 && tail * 10 < cus * 3 && r_big > 0 && r_big < rm && !d->amax_out &&
-                g16_split_rows(*d, r_big * 256, d1, d2)) {
-                DUPL_LAUNCH((gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>), dim3((unsigned)(r_big * cn)), dim3(512), 0, s, d1, g16_group_ring);
-                DUPL_LAUNCH((gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>), dim3((unsigned)(((d2.M + 255) / 256) * ((d2.N + 127) / 128))),
-                            dim3(512), 0, s, d2, g16_group_ring);
-            } else DUPL_LAUNCH((gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>), blocks(256, 256), dim3(512), 0, s, *d, g16_group_ring);
-        }
-        else if (t == 22) DUPL_LAUNCH((gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
+        if (t == 18 || t == 22)
+            g16_launch16(*d, t, g16_tile == 0, g16_group_ring, s, gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>, gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>);
         else if (t == 8) DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 4, 2, 2, true>), blocks(256, 256), dim3(512), 0, s, *d, g16_group_ring);
         else if (t == 12) DUPL_LAUNCH((gemm_f16x3_ring_kernel<2, 2, 4, 2, 2, 3, true>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
         else
@@ -2200,32 +2052,13 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
     return dupl_launch_status();
 }
 
-// products = 1: the single-product forward (gemm_f16_ring16_kernel).  Both tiles carry the same bits, so the automatic choice and its
-// row split are the format 1 forward's (see there): 256 x 256 where the grid fills the chip, the rows of a thin last round on 256 x 128.
+// products = 1: the single-product forward, gemm_f16x3_ring16_kernel<.., NP = 1> on the tiles and with the row split of the format 1
+// forward (g16_launch16).
 #ifndef G16H_STAGES
 #define G16H_STAGES 4   // ring depth of both tiles (4 x 32 KB / 4 x 24 KB)
 #endif
 static int g16_launch_hi(const dupl_gemm16_desc& d, const int tile, const int group, hipStream_t s) {
-    const int cn = (d.N + 255) / 256, rm = (d.M + 255) / 256, cus = 256;
-    const int nb22 = rm * cn;
-    const int t = (tile == 18 || tile == 22) ? tile : (nb22 >= G16_F1_BIG_FROM ? 18 : 22);
-    auto small = [&](const dupl_gemm16_desc& q) {
-        DUPL_LAUNCH((gemm_f16_ring16_kernel<2, 2, 4, 2, 2, G16H_STAGES>), dim3((unsigned)(((q.M + 255) / 256) * ((q.N + 127) / 128))), dim3(512), 0,
-                    s, q, group);
-    };
-    auto big = [&](const dupl_gemm16_desc& q) {
-        DUPL_LAUNCH((gemm_f16_ring16_kernel<4, 2, 2, 4, 2, G16H_STAGES>), dim3((unsigned)(((q.M + 255) / 256) * cn)), dim3(512), 0, s, q, group);
-    };
-    if (t == 22) small(d);
-    else {
-        const int full = nb22 / cus, tail = nb22 - full * cus;
-        const int r_big = full > 0 ? (full * cus) / cn : 0;
-        dupl_gemm16_desc d1, d2;
-        if (tile == 0 && full > 0 && tail > 0 && tail * 10 < cus * 3 && r_big > 0 && r_big < rm && !d.amax_out &&
-            g16_split_rows(d, r_big * 256, d1, d2)) {
-            big(d1);
-            small(d2);
-        } else big(d);
-    }
+    const g16_kernel_t small = gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, G16H_STAGES, 1>, big = gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, G16H_STAGES, 1>;
+    g16_launch16(d, (tile == 18 || tile == 22) ? tile : g16_tile16(d), tile == 0, group, s, big, small);
     return dupl_launch_status();
 }

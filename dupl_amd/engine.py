@@ -41,7 +41,7 @@ def set_gemm_mode(mode: str):
 # The no-grad encoder passes (_encoder_forward16(save=False): the multi-scale CAM passes of a step, validation, tools/infer_cam, the
 # encoder part of tools/eval_seg) may trade precision for rate: "f16" runs every site the RangeGuard leaves on planes -- patch
 # embedding, qkv, proj, fc1, fc2 and the attention -- as ONE f16 product on the hi planes with fp32 accumulation
-# (gemm_f16_ring16_kernel, attn_fwd16_h1_kernel) instead of three.  Opt-in (DUPL_NOGRAD_GEMM=f16 or set_nograd_gemm_mode); the
+# (the NP = 1 instantiations of gemm_f16x3_ring16_kernel and attn_fwd16_m16_kernel) instead of three.  Opt-in (DUPL_NOGRAD_GEMM=f16 or set_nograd_gemm_mode); the
 # default "f16x3" changes nothing.  Applies only while GEMM_MODE == "f16x3"; a pass that saves anything for the backward, the CAM
 # heads and the LargeFOV convs never run single-product.
 NOGRAD_GEMM = os.environ.get("DUPL_NOGRAD_GEMM", "f16x3")

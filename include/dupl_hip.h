@@ -137,7 +137,7 @@ typedef struct dupl_gemm16_desc {
                                              shared in L2; an n that does not fit a launch's shape -- more units than blocks, a slice under 3 k-steps -- is
                                              replaced by the library's choice); 0 = the library picks n from the grid; < 0 = equal runs of (tile, k-step) pairs */
     int32_t products;                     /* f16 products per block of the k-contiguous forward: 0 or 3 = f16x3 (hi.hi + hi.lo + lo.hi, fp32-equivalent);
-                                             1 = hi.hi only (gemm_f16_ring16_kernel on v_mfma_f32_16x16x32_f16: the operands rounded to fp16, fp32
+                                             1 = hi.hi only (gemm_f16x3_ring16_kernel<.., NP = 1> on v_mfma_f32_16x16x32_f16: the operands rounded to fp16, fp32
                                              accumulation, the same epilogue and outputs) -- then A_lo / B_lo are not read and may be NULL, tile is
                                              0, 18 (256x256) or 22 (256x128), and DUPL_GEMM_ACCUM and k-major operands are refused.  Anything else
                                              is DUPL_ERR_ARG.  (Was reserved1: callers that zeroed it keep today's kernels.) */
@@ -277,7 +277,7 @@ int dupl_attention_fwd16_mfma(const void* qkv_hi, const void* qkv_lo, float* out
 int dupl_attention_fwd16_segs_mfma(const void* qkv_hi, const void* qkv_lo, void* out_hi, void* out_lo, const dupl_attn_seg* segs,
                                    int32_t n, int32_t H, int32_t hd, float scale, int32_t out_exp, int32_t mfma, dupl_stream_t s);
 /* The same two entry points with the number of f16 products as one more argument: 3 = the f16x3 attention above (what every entry
- * point above passes), 1 = attn_fwd16_h1_kernel: S = q_hi k_hi^T, softmax in fp32 with the same lazy running maximum, the
+ * point above passes), 1 = attn_fwd16_m16_kernel<1>: S = q_hi k_hi^T, softmax in fp32 with the same lazy running maximum, the
  * probabilities rounded to ONE fp16 plane, O = P_hi v_hi (v_mfma_f32_16x16x32_f16, fp32 accumulation) -- the no-grad mode: the lo
  * plane of qkv is not read (qkv_lo may be NULL), lse must be NULL (every segment's too) and mfma 0 or 16.  Outputs as above (fp32
  * and / or planes in either format).  products outside {1, 3} is DUPL_ERR_ARG before the launch. */

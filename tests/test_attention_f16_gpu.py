@@ -1,4 +1,4 @@
-"""-m gpu: the single-product attention forward (csrc/attn_split.hip attn_fwd16_h1_kernel; `products` = 1 of
+"""-m gpu: the single-product attention forward (csrc/attn_split.hip attn_fwd16_m16_kernel<1>; `products` = 1 of
 dupl_attention_fwd16_prod / dupl_attention_fwd16_segs_prod, ops.attention_fwd16(.., products=1)): S = q_hi k_hi^T, softmax in fp32
 with the lazy running maximum of attn_fwd16_m16_kernel, the probabilities rounded to ONE fp16 plane, O = P_hi v_hi.
 

@@ -1,4 +1,4 @@
-"""-m gpu: the single-product forward GEMM (dupl_gemm16_desc.products = 1; csrc/gemm_split.hip gemm_f16_ring16_kernel, tiles 18:
+"""-m gpu: the single-product forward GEMM (dupl_gemm16_desc.products = 1; csrc/gemm_split.hip gemm_f16x3_ring16_kernel<.., NP = 1>, tiles 18:
 256 x 256 and 22: 256 x 128, four LDS stages each): C = act(alpha * post_scale * A_hi . B_hi^T + bias) (+ res), fp32 accumulation.
 
   1  against the fp64 product of the DECODED HI PLANES the kernel reads (+ the epilogue in fp64), inside the project's bar for an

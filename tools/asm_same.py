@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Compare the kernels of two device assembly files (hipcc ... --cuda-device-only -S), symbol by symbol:
-    tools/asm_same.py parent.s new.s
-A kernel is SAME when the text between its label and its .Lfunc_end label and its .amdhsa_kernel block are identical."""
+    tools/asm_same.py [--map OLD=NEW]... parent.s new.s
+A kernel is SAME when the text between its label and its .Lfunc_end label and its .amdhsa_kernel block are identical.
+--map (repeatable) renames on the parent side before the comparison: every occurrence of OLD, a substring of a symbol, becomes NEW."""
 import re
 import sys
 
 
-def kernels(path):
+def kernels(path, maps=()):
     s = open(path).read()
+    for old, new in maps:
+        s = s.replace(old, new)
     out = {}
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", s, re.M | re.S):
         name, hsa = m.group(1), m.group(2)
@@ -18,7 +21,12 @@ def kernels(path):
     return out
 
 
-a, b = kernels(sys.argv[1]), kernels(sys.argv[2])
+args, maps = sys.argv[1:], []
+while "--map" in args:
+    i = args.index("--map")
+    maps.append(tuple(args[i + 1].split("=", 1)))
+    del args[i:i + 2]
+a, b = kernels(args[0], maps), kernels(args[1])
 print(f"{'':4} {'lines':>6} {'vgpr':>5} {'sgpr':>5} {'scratch':>7} {'lds':>7}  kernel")
 for name in sorted(set(a) | set(b)):
     same = name in a and name in b and a[name][:2] == b[name][:2]

@@ -1,4 +1,4 @@
-// Stand-alone timing of the split attention forward (csrc/attn_split.hip) through the C ABI.
+// Stand-alone timing of the split attention forward (csrc/attn_split.hip) and backward (csrc/attn_split_bwd.hip) through the C ABI.
 //   default        the four single-batch cases with the kernel chosen by -m (0 = the library's choice, 32, 16); with an ATT_ABL=16
 //                  build of the library (LD_LIBRARY_PATH) -d prints the per-phase cycle sums of wave 0: wait + barrier / QK^T /
 //                  softmax / PV
@@ -6,6 +6,9 @@
 //                  cases, then the step's segmented launch ((8, 1765), (8, 197)) in one stream and next to a second stream that
 //                  runs the same launch.  Per case: median / min / max of each kernel's rounds, its spread (max - min) / median, and
 //                  the ratio of the medians.
+//   -b [-r R]      the BACKWARD (dupl_attention_bwd16: delta + the two-role launch) at H = 12, B x N = 4 x 785 (the step), 2 x 785,
+//                  8 x 785, 4 x 197: random planes, out / lse from the forward, the dO planes and scale record from the real split; each
+//                  case in one stream and next to a second stream, median / min / max of R rounds
 //   -s             the segmented launch alone, one stream, kernel -m, one -w window (what a counter pass is taken on)
 // build: hipcc -O2 --offload-arch=gfx950 -Iinclude tools/attn16_bench.cpp -Ldupl_amd -ldupl_hip -Wl,-rpath,'$ORIGIN/../dupl_amd' -o tools/attn16_bench
 #include <hip/hip_runtime.h>
@@ -108,6 +111,51 @@ static int compare(int rounds, int window_ms) {
     return 0;
 }
 
+// Everything one backward call needs, made the way a step makes it: q / k / v planes of random data, out and lse from the forward,
+// a random dout of a step's magnitude, its planes and scale record from the real split (dupl_split_prepare, target_exp 4).
+struct Bwd {
+    Planes p; int B, N; float *out, *dout, *lse, *delta, *dqkv, *slot; __half* do16; long no;
+    Bwd(int B_, int N_, uint32_t seed, hipStream_t st) : p((long)B_ * N_, seed), B(B_), N(N_) {
+        no = (long)B * N * D;
+        CK(hipMalloc(&out, no * 4)); CK(hipMalloc(&dout, no * 4)); CK(hipMalloc(&do16, no * 4)); CK(hipMalloc(&dqkv, p.nq * 4));
+        CK(hipMalloc(&lse, (long)B * H * N * 4)); CK(hipMalloc(&delta, (long)B * H * N * 4)); CK(hipMalloc(&slot, 32));
+        CK(hipMemset(slot, 0, 32));
+        fill_kernel<<<1024, 256>>>(dout, no, seed + 1, 2e-5f);
+        if (dupl_attention_fwd16_mfma(p.q16, p.q16 + p.nq, out, nullptr, nullptr, lse, B, N, H, hd, 0.125f, 0, 0, 0, st)) { fprintf(stderr, "forward failed\n"); exit(2); }
+        dupl_split_desc d; memset(&d, 0, sizeof d);
+        d.struct_size = sizeof d; d.x = dout; d.ld = D; d.R = B * N; d.C = D; d.slot = slot; d.next_bits = slot + 6;
+        d.hi = do16; d.lo = do16 + no; d.Rp = (B * N + 31) / 32 * 32; d.target_exp = 4;
+        if (dupl_split_prepare(&d, st)) { fprintf(stderr, "split failed\n"); exit(2); }
+        CK(hipDeviceSynchronize());
+    }
+    int run(hipStream_t st) const {
+        return dupl_attention_bwd16(p.q16, p.q16 + p.nq, out, dout, do16, do16 + no, slot, lse, delta, dqkv, B, N, H, hd, 0.125f, nullptr, st);
+    }
+    ~Bwd() { hipFree(out); hipFree(dout); hipFree(do16); hipFree(dqkv); hipFree(lse); hipFree(delta); hipFree(slot); }
+};
+
+// -b: dupl_attention_bwd16 (the delta launch + the dq / dk + dv launch), each case in one stream and next to a second stream that runs
+// the same call on its own buffers.  Two builds of the library are compared by alternating two runs of this mode (LD_LIBRARY_PATH).
+static int time_bwd(int rounds, int window_ms) {
+    hipStream_t st, st2; CK(hipStreamCreate(&st)); CK(hipStreamCreate(&st2));
+    printf("backward, time per call, us: median / min / max of %d rounds, spread = (max - min) / median\n", rounds);
+    const int cases[][2] = {{4, 785}, {2, 785}, {8, 785}, {4, 197}};
+    for (auto& c : cases) {
+        Bwd a(c[0], c[1], 7, st), b(c[0], c[1], 17, st);
+        for (int two = 0; two < 2; ++two) {
+            std::vector<double> t;
+            for (int r = 0; r < rounds; ++r) {
+                auto run = [&]() { int e = a.run(st); if (two && !e) e = b.run(st2); return e; };
+                t.push_back(time_us(run, window_ms));
+            }
+            std::sort(t.begin(), t.end());
+            printf("B=%d N=%4d, %-11s | %7.1f %7.1f %7.1f  %5.2f%%\n", c[0], c[1], two ? "two streams" : "one stream", t[t.size() / 2], t.front(),
+                   t.back(), (t.back() - t.front()) / t[t.size() / 2] * 100);
+        }
+    }
+    return 0;
+}
+
 static int segs_only(int mfma, int window_ms) {
     hipStream_t st; CK(hipStreamCreate(&st));
     const long rows = 8L * 1765 + 8L * 197;
@@ -121,16 +169,18 @@ static int segs_only(int mfma, int window_ms) {
 }
 
 int main(int argc, char** argv) {
-    bool dbg = false, cmp = false, sgo = false;
+    bool dbg = false, cmp = false, sgo = false, bwd = false;
     int window_ms = 200, mfma = 0, rounds = 5;
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "-d")) dbg = true;
         else if (!strcmp(argv[i], "-c")) cmp = true;
         else if (!strcmp(argv[i], "-s")) sgo = true;
+        else if (!strcmp(argv[i], "-b")) bwd = true;
         else if (!strcmp(argv[i], "-w") && i + 1 < argc) window_ms = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-m") && i + 1 < argc) mfma = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-r") && i + 1 < argc) rounds = std::max(1, atoi(argv[++i]));
     }
+    if (bwd) return time_bwd(rounds, window_ms);
     if (cmp) return compare(rounds, window_ms);
     if (sgo) return segs_only(mfma, window_ms);
     const int cases[][2] = {{8, 1765}, {8, 785}, {8, 197}, {4, 785}};

@@ -682,20 +682,50 @@ def encoder_forward(P: StudentParams, x: Tensor, save: bool, save_rows: int = 0)
     """forward_features (vit.py:308-326).  Returns (tokens_final [B*(1+n), D], tokens_aux [B*(1+n), D], saved).
     tokens_aux = output of block `aux_layer` (un-normalised unless it is the last block).
     save_rows: only the first save_rows token rows will be back-propagated (f16x3 mode: their fp32 copies only)."""
+    return _encoder_pass(P, [x], save, save_rows)[0]
+
+
+def _encoder_pass(P: StudentParams, xs, save: bool, save_rows: int = 0, whole: bool = False):
+    """forward_features of one or several batches in the current GEMM_MODE (_encoder_forward16's calling convention)."""
     if GEMM_MODE == "f16x3":
-        return _encoder_forward16(P, [x], save, save_rows)[0]
+        return _encoder_forward16(P, xs, save, save_rows, whole)
+    return _encoder_forward32(P, xs, save, whole)
+
+
+def _assemble_tokens(P: StudentParams, xs, embed):
+    """Patch rows -> tokens of every batch of a pass, concatenated: cls token + embed(patch rows) + resized pos-embed.
+    embed: the patch-embedding Linear of the caller's GEMM mode (fp32 rows [B*n, 3*patch^2] -> fp32 [B*n, D]).
+    Returns (t [sum_i B_i*(1+n_i), D], [(row0, B, 1+n, h, w)] per batch)."""
     cfg = P.cfg
-    B, _, Himg, Wimg = x.shape
-    h, w = Himg // cfg.patch, Wimg // cfg.patch
-    n, D, H, hd = h * w, cfg.embed_dim, cfg.num_heads, cfg.head_dim
-    N = n + 1
+    toks, groups = [], []
+    r0 = 0
+    for x in xs:
+        B, _, Himg, Wimg = x.shape
+        h, w = Himg // cfg.patch, Wimg // cfg.patch
+        n = h * w
+        patch = embed(ops.patch_im2row(x, cfg.patch))
+        toks.append(ops.assemble_tokens(patch, P.w["encoder.cls_token"], P.pos_embed_for(h, w), B, n, cfg.embed_dim))
+        del patch
+        groups.append((r0, B, n + 1, h, w))
+        r0 += B * (n + 1)
+    t = torch.cat(toks, dim=0) if len(toks) > 1 else toks[0]
+    return t, groups
+
+
+def _encoder_forward32(P: StudentParams, xs, save: bool, whole: bool = False):
+    """_encoder_forward16's pass on the exact-f32 MFMA kernels: every row-wise kernel once over the concatenated token rows of
+    all batches, attention per batch on its row slice.  lse, the LayerNorm statistics and pre1 exist only with save (single
+    batch only).  Returns [(tokens_final, tokens_aux, saved)] per batch (row-slice views)."""
+    assert not (save and len(xs) > 1), "the exact-f32 pass saves a single batch only"
+    cfg = P.cfg
+    D, H, hd = cfg.embed_dim, cfg.num_heads, cfg.head_dim
     W = P.w
-    rows = ops.patch_im2row(x, cfg.patch)
-    patch = ops.linear(rows, W["encoder.patch_embed.proj.weight"], W["encoder.patch_embed.proj.bias"])
-    del rows
-    t = ops.assemble_tokens(patch, W["encoder.cls_token"], P.pos_embed_for(h, w), B, n, D)
-    del patch
-    sv = EncoderSaved(B=B, h=h, w=w, x_img=x if save else None) if save else None
+    t, groups = _assemble_tokens(P, xs, lambda rows: ops.linear(rows, W["encoder.patch_embed.proj.weight"],
+                                                                W["encoder.patch_embed.proj.bias"]))
+    sv = None
+    if save:
+        _, B, _, h, w = groups[0]
+        sv = EncoderSaved(B=B, h=h, w=w, x_img=xs[0])
     aux_idx = cfg.aux_layer % cfg.depth
     aux = None
     scale = hd ** -0.5
@@ -703,7 +733,9 @@ def encoder_forward(P: StudentParams, x: Tensor, save: bool, save_rows: int = 0)
         p = f"encoder.blocks.{i}."
         ln1, m1, r1 = ops.layernorm_fwd(t, W[p + "norm1.weight"], W[p + "norm1.bias"], cfg.ln_eps, save)
         qkv = ops.linear(ln1, W[p + "attn.qkv.weight"], W[p + "attn.qkv.bias"])
-        att, lse = ops.attention_fwd(qkv, B, N, H, hd, scale, need_lse=save)
+        att = torch.empty((t.shape[0], D), device=t.device, dtype=torch.float32)
+        for (g0, B, N, _, _) in groups:
+            _, lse = ops.attention_fwd(qkv[g0:g0 + B * N], B, N, H, hd, scale, need_lse=save, out=att[g0:g0 + B * N])
         x_mid = ops.linear(att, W[p + "attn.proj.weight"], W[p + "attn.proj.bias"], res=t)
         ln2, m2, r2 = ops.layernorm_fwd(x_mid, W[p + "norm2.weight"], W[p + "norm2.bias"], cfg.ln_eps, save)
         pre1 = torch.empty((t.shape[0], D * cfg.mlp_ratio), device=t.device, dtype=torch.float32) if save else None
@@ -720,7 +752,10 @@ def encoder_forward(P: StudentParams, x: Tensor, save: bool, save_rows: int = 0)
         sv.x_last, sv.mean_f, sv.rstd_f = t, mf, rf
     if aux is None:  # aux_layer == last block -> embeds[-1] is the final LN output (vit.py:323-324)
         aux = tf
-    return tf, aux, sv
+    outs = [(tf[g0:g0 + B * N], aux[g0:g0 + B * N], sv) for (g0, B, N, _, _) in groups]
+    if whole:
+        return outs, tf, aux
+    return outs
 
 
 def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, whole: bool = False):
@@ -748,25 +783,13 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
     assert not (save and len(xs) > 1 and not save_rows), "a merged pass can only save a row prefix of its first batch (partial_save_ok)"
     def ea(site_flags, site):             # plane format (format 1 exponent, 0 = format 0) of the activations that feed `site`'s GEMM
         return int(site_flags[site + "_f1"]) if FMT1 else 0
-    toks, groups = [], []
-    r0 = 0
-    for x in xs:
-        B, _, Himg, Wimg = x.shape
-        h, w = Himg // cfg.patch, Wimg // cfg.patch
-        n = h * w
-        if guard["patch"]:
-            e = ea(guard, "patch")
-            rows16 = ops.split16(ops.patch_im2row(x, cfg.patch), exp=e)
-            patch, _ = _lin16(P, rows16, P.w16("encoder.patch_embed.proj.weight", D, bool(e)), W["encoder.patch_embed.proj.bias"],
-                             products=prod)
-            del rows16
-        else:
-            patch = ops.linear(ops.patch_im2row(x, cfg.patch), W["encoder.patch_embed.proj.weight"], W["encoder.patch_embed.proj.bias"])
-        toks.append(ops.assemble_tokens(patch, W["encoder.cls_token"], P.pos_embed_for(h, w), B, n, D))
-        groups.append((r0, B, n + 1, h, w))
-        r0 += B * (n + 1)
-    t = torch.cat(toks, dim=0) if len(toks) > 1 else toks[0]
-    del toks
+    def embed(rows):                      # the patch Linear: on planes unless the guard routed it to exact f32
+        if not guard["patch"]:
+            return ops.linear(rows, W["encoder.patch_embed.proj.weight"], W["encoder.patch_embed.proj.bias"])
+        e = ea(guard, "patch")
+        return _lin16(P, ops.split16(rows, exp=e), P.w16("encoder.patch_embed.proj.weight", D, bool(e)),
+                      W["encoder.patch_embed.proj.bias"], products=prod)[0]
+    t, groups = _assemble_tokens(P, xs, embed)
     R = t.shape[0]
     sv = None
     if save:
@@ -802,31 +825,26 @@ def _encoder_forward16(P: StudentParams, xs, save: bool, save_rows: int = 0, who
         need_att32 = save or not g["proj"]
         att = torch.empty((save_rows or R, D), device=t.device, dtype=torch.float32) if (need_att32 or not attn16) else None
         att16 = ops.split16_empty(R, D, t.device, ea(g, "proj")) if (attn16 and g["proj"]) else None
-        lse = None
         use_segs = attn16 and 1 < len(groups) <= ops._lib.ATTN_SEGS_MAX and \
             sum(B_ * H * ((N_ + 127) // 128) for (_, B_, N_, _, _) in groups) <= ATTN_SEGS
+        # per batch (row0, B, N, fp32 out slice or None, need_lse, b_f32): only batch 0 is ever back-propagated (lse), and of it only
+        # the first b_f32 images when the pass saves a row prefix -- rows beyond that prefix leave as planes only
+        plan = []
+        for gi, (g0, B, N, _, _) in enumerate(groups):
+            planes_only = bool(save_rows and gi > 0) or att is None
+            bf = save_rows // N if (save_rows and gi == 0) else 0
+            plan.append((g0, B, N, None if planes_only else att[g0:g0 + (bf or B) * N], bool(save and gi == 0), bf))
         if use_segs:
             # every batch of the pass in one launch, longest first (dupl_attention_fwd16_segs): the short batches fill the tails
-            segs = []
-            for gi, (g0, B, N, _, _) in enumerate(groups):
-                planes_only = bool(save_rows and gi > 0) or att is None
-                bf = save_rows // N if (save_rows and gi == 0) else 0
-                segs.append((g0, B, N, None if planes_only else att[g0:g0 + (bf or B) * N], bool(save and gi == 0), bf))
-            lse = ops.attention_fwd16_segs(qkv16, segs, H, hd, scale, out16=att16, products=prod)[0]
-        for gi, (g0, B, N, _, _) in enumerate(() if use_segs else groups):
+            lse = ops.attention_fwd16_segs(qkv16, plan, H, hd, scale, out16=att16, products=prod)[0]
+        for (g0, B, N, out, need_lse, bf) in (() if use_segs else plan):
             if attn16:
-                if save_rows and gi > 0:      # rows beyond the saved prefix: planes only, no fp32 output, no lse
-                    ops.attention_fwd16(qkv16.rows_slice(g0, g0 + B * N), B, N, H, hd, scale, need_lse=False, out=None,
-                                        out16=att16.rows_slice(g0, g0 + B * N), products=prod)
-                    continue
-                bf = save_rows // N if save_rows else 0
-                lse_g = ops.attention_fwd16(qkv16.rows_slice(g0, g0 + B * N), B, N, H, hd, scale, need_lse=save,
-                                            out=att[g0:g0 + (bf or B) * N] if att is not None else None,
+                lse_g = ops.attention_fwd16(qkv16.rows_slice(g0, g0 + B * N), B, N, H, hd, scale, need_lse=need_lse, out=out,
                                             out16=att16.rows_slice(g0, g0 + B * N) if att16 is not None else None, b_f32=bf,
                                             products=prod)
             else:   # other head dims (the 96-dim test backbone) or q / k / v beyond fp16's range: exact-f32 attention kernel
-                _, lse_g = ops.attention_fwd(qkv[g0:g0 + B * N], B, N, H, hd, scale, need_lse=save, out=att[g0:g0 + B * N])
-            if gi == 0:
+                _, lse_g = ops.attention_fwd(qkv[g0:g0 + B * N], B, N, H, hd, scale, need_lse=need_lse, out=out)
+            if g0 == 0:
                 lse = lse_g
         if not attn16 and g["proj"]:
             att16 = ops.split16(att, exp=ea(g, "proj"))
@@ -889,15 +907,25 @@ def partial_save_ok(P: StudentParams, guard=None) -> bool:
     return all(b[k] for b in guard["blocks"] for k in RangeGuard.SITES)
 
 
+def _cam_heads(P: StudentParams, outs, tf: Tensor, aux: Tensor):
+    """The CAM heads of an encoder pass (`outs, tf, aux` = its whole=True return value).  They stay on the f32 kernel in both
+    modes (N = C columns): one launch each over the rows of all batches (which ARE one tensor).
+    Returns [(cam_aux_tok, cam_tok)] per batch (row-slice views)."""
+    C = P.num_classes - 1
+    cam = ops.linear(tf, P.w["classifier.weight"].view(C, -1))
+    cam_aux = ops.linear(aux, P.w["aux_classifier.weight"].view(C, -1))
+    res, g0 = [], 0
+    for o in outs:
+        r = o[0].shape[0]
+        res.append((cam_aux[g0:g0 + r], cam[g0:g0 + r]))
+        g0 += r
+    return res
+
+
 def cam_logits(P: StudentParams, x: Tensor):
     """cam_only path (model_dupl.py:81-84), token-major: returns (cam_aux_tok, cam_tok), each
     [B*(1+n), C] (row 0 of every image is the cls token and must be skipped), plus (h, w)."""
-    tf, aux, _ = encoder_forward(P, x, save=False)
-    Wc = P.w["classifier.weight"].view(P.num_classes - 1, -1)
-    Wa = P.w["aux_classifier.weight"].view(P.num_classes - 1, -1)
-    cam = ops.linear(tf, Wc)
-    cam_aux = ops.linear(aux, Wa)
-    return cam_aux, cam
+    return cam_logits_multi(P, [x])[0]
 
 
 def cam_logits_multi(P: StudentParams, xs):
@@ -906,57 +934,7 @@ def cam_logits_multi(P: StudentParams, xs):
     ms-CAM scale alone is 1 576 rows = 150-600 GEMM blocks on 256 CUs; merged with the 1.5x scale it rides in a
     15 696-row GEMM) and only attention, which mixes tokens of one image, runs per batch on its row slice.  Row-wise
     ops make this bit-identical to separate passes.  Returns [(cam_aux_tok, cam_tok)] per batch (row-slice views)."""
-    cfg = P.cfg
-    D, H, hd = cfg.embed_dim, cfg.num_heads, cfg.head_dim
-    W = P.w
-    if GEMM_MODE == "f16x3":
-        C = P.num_classes - 1
-        outs, tf_all, aux_all = _encoder_forward16(P, list(xs), save=False, whole=True)
-        # the CAM heads (N = C columns) stay on the f32 kernel: one launch over the rows of all batches (which ARE one tensor)
-        cam = ops.linear(tf_all, W["classifier.weight"].view(C, -1))
-        cam_aux = ops.linear(aux_all, W["aux_classifier.weight"].view(C, -1))
-        res, g0 = [], 0
-        for o in outs:
-            r = o[0].shape[0]
-            res.append((cam_aux[g0:g0 + r], cam[g0:g0 + r]))
-            g0 += r
-        return res
-    toks, groups = [], []
-    r0 = 0
-    for x in xs:
-        B, _, Himg, Wimg = x.shape
-        h, w = Himg // cfg.patch, Wimg // cfg.patch
-        n = h * w
-        rows = ops.patch_im2row(x, cfg.patch)
-        patch = ops.linear(rows, W["encoder.patch_embed.proj.weight"], W["encoder.patch_embed.proj.bias"])
-        toks.append(ops.assemble_tokens(patch, W["encoder.cls_token"], P.pos_embed_for(h, w), B, n, D))
-        groups.append((r0, B, n + 1))
-        r0 += B * (n + 1)
-    t = torch.cat(toks, dim=0) if len(toks) > 1 else toks[0]
-    del toks
-    aux_idx = cfg.aux_layer % cfg.depth
-    aux = None
-    scale = hd ** -0.5
-    for i in range(cfg.depth):
-        p = f"encoder.blocks.{i}."
-        ln1, _, _ = ops.layernorm_fwd(t, W[p + "norm1.weight"], W[p + "norm1.bias"], cfg.ln_eps, False)
-        qkv = ops.linear(ln1, W[p + "attn.qkv.weight"], W[p + "attn.qkv.bias"])
-        att = torch.empty((t.shape[0], D), device=t.device, dtype=torch.float32)
-        for (g0, B, N) in groups:
-            ops.attention_fwd(qkv[g0:g0 + B * N], B, N, H, hd, scale, out=att[g0:g0 + B * N])
-        x_mid = ops.linear(att, W[p + "attn.proj.weight"], W[p + "attn.proj.bias"], res=t)
-        ln2, _, _ = ops.layernorm_fwd(x_mid, W[p + "norm2.weight"], W[p + "norm2.bias"], cfg.ln_eps, False)
-        h1 = ops.linear(ln2, W[p + "mlp.fc1.weight"], W[p + "mlp.fc1.bias"], gelu=True)
-        t = ops.linear(h1, W[p + "mlp.fc2.weight"], W[p + "mlp.fc2.bias"], res=x_mid)
-        if i == aux_idx and i != cfg.depth - 1:
-            aux = t
-    tf, _, _ = ops.layernorm_fwd(t, W["encoder.norm.weight"], W["encoder.norm.bias"], cfg.ln_eps, False)
-    if aux is None:
-        aux = tf
-    C = P.num_classes - 1
-    cam = ops.linear(tf, W["classifier.weight"].view(C, -1))
-    cam_aux = ops.linear(aux, W["aux_classifier.weight"].view(C, -1))
-    return [(cam_aux[g0:g0 + B * N], cam[g0:g0 + B * N]) for (g0, B, N) in groups]
+    return _cam_heads(P, *_encoder_pass(P, list(xs), save=False, whole=True))
 
 
 @dataclass
@@ -1009,15 +987,11 @@ def cam_logits_shared(P: StudentParams, x2: Tensor, b: int):
     it twice: cam_helper.py:171 under no_grad, then train_final_voc.py:204).  The whole 2b batch goes through the
     kernels in one piece (large grids); the cache handed back is the row-prefix view of the un-flipped half.
     Returns (cam_aux_tok, cam_tok) [2b*(1+n), C] and the cache (tf, aux, EncoderSaved)."""
-    C = P.num_classes - 1
-    Wc = P.w["classifier.weight"].view(C, -1)
-    Wa = P.w["aux_classifier.weight"].view(C, -1)
     rows = (x2.shape[0] // 2) * ((x2.shape[2] // P.cfg.patch) * (x2.shape[3] // P.cfg.patch) + 1)
-    tf, aux, enc = encoder_forward(P, x2, save=True, save_rows=rows)
-    cam = ops.linear(tf, Wc)
-    cam_aux = ops.linear(aux, Wa)
+    outs, tf, aux = _encoder_pass(P, [x2], save=True, save_rows=rows, whole=True)
+    (cam_aux, cam), = _cam_heads(P, outs, tf, aux)
     assert rows == tf.shape[0] // 2
-    return cam_aux, cam, (tf[:rows], aux[:rows], _prefix_saved(enc, b, rows))
+    return cam_aux, cam, (tf[:rows], aux[:rows], _prefix_saved(outs[0][2], b, rows))
 
 
 def cam_logits_shared_multi(P: StudentParams, xs, b: int):
@@ -1027,7 +1001,6 @@ def cam_logits_shared_multi(P: StudentParams, xs, b: int):
     6 280-row pass and a 15 696-row pass: half the launches, larger GEMM grids.  Row-wise kernels and per-batch attention make the
     result bit-identical to the separate passes.  Needs partial_save_ok(P).
     Returns [(cam_aux_tok, cam_tok)] per batch and the training forward's cache (tf, aux, EncoderSaved) of x = xs[0][:b]."""
-    C = P.num_classes - 1
     n0 = (xs[0].shape[2] // P.cfg.patch) * (xs[0].shape[3] // P.cfg.patch) + 1
     rows = (xs[0].shape[0] // 2) * n0
     P.store.ensure_w16(P.student)         # (takes in the range guard's verdicts: the check below must see what the pass will run with)
@@ -1037,15 +1010,14 @@ def cam_logits_shared_multi(P: StudentParams, xs, b: int):
         cam_aux_t, cam_t, cache = cam_logits_shared(P, xs[0], b)
         return [(cam_aux_t, cam_t)] + (cam_logits_multi(P, xs[1:]) if len(xs) > 1 else []), cache
     outs, tf, aux = _encoder_forward16(P, list(xs), save=True, save_rows=rows, whole=True)
-    enc = outs[0][2]
-    cam = ops.linear(tf, P.w["classifier.weight"].view(C, -1))
-    cam_aux = ops.linear(aux, P.w["aux_classifier.weight"].view(C, -1))
-    res, g0 = [], 0
-    for o in outs:
-        r = o[0].shape[0]
-        res.append((cam_aux[g0:g0 + r], cam[g0:g0 + r]))
-        g0 += r
-    return res, (tf[:rows], aux[:rows], _prefix_saved(enc, b, rows))
+    return _cam_heads(P, outs, tf, aux), (tf[:rows], aux[:rows], _prefix_saved(outs[0][2], b, rows))
+
+
+def _conv_col32(src_ptr, dev, B: int, h: int, w: int, Cin: int, dil: int, ld: int, img_stride: int, Wmat: Tensor):
+    """One 3x3 dilated conv + ReLU on the exact-f32 kernels: im2col into an fp32 col, GEMM with fused ReLU.  Returns (h, col)."""
+    col = torch.empty((B * h * w, 9 * Cin), device=dev, dtype=torch.float32)
+    ops.L().dupl_im2col_dil3(src_ptr, col.data_ptr(), B, h, w, Cin, dil, ld, img_stride, ops._stream())
+    return ops.linear(col, Wmat, relu=True), col
 
 
 def network_forward(P: StudentParams, x: Tensor, save: bool, enc_cache=None):
@@ -1079,15 +1051,15 @@ def network_forward(P: StudentParams, x: Tensor, save: bool, enc_cache=None):
     def conv(site, src_ptr, Cin, ld, img_stride):
         """One 3x3 dilated conv + ReLU; returns (h, fp32 col | None, col^T planes | None)."""
         Wk = f"decoder.{site}.weight"
-        if f16 and guard[site] and (DECODER_PLANES & 1) and Cin % 8 == 0:
+        if not (f16 and guard[site]):      # exact-f32 mode, or the guard routed the site to exact f32
+            return (*_conv_col32(src_ptr, x.device, B, h, w, Cin, dil, ld, img_stride, P.w[Wk].view(dd, -1)), None)
+        if (DECODER_PLANES & 1) and Cin % 8 == 0:
             # on planes: im2col writes the GEMM's A planes and (for the backward's weight gradient) their transpose; no fp32 col
             c16, cT16 = ops.im2col_dil3_planes(src_ptr, x.device, B, h, w, Cin, dil, ld, img_stride, want_T=save, rows_pad=Mp)
             return _lin16(P, c16, P.w16(Wk, dd), relu=True)[0], None, cT16
         col = torch.empty((B * n, 9 * Cin), device=x.device, dtype=torch.float32)
         ops.L().dupl_im2col_dil3(src_ptr, col.data_ptr(), B, h, w, Cin, dil, ld, img_stride, ops._stream())
-        if f16 and guard[site]:
-            return _lin16(P, ops.split16(col), P.w16(Wk, dd), relu=True)[0], col, None
-        return ops.linear(col, P.w[Wk].view(dd, -1), relu=True), col, None      # the guard routed the site to exact f32
+        return _lin16(P, ops.split16(col), P.w16(Wk, dd), relu=True)[0], col, None
 
     h6, col6, col6T = conv("conv6", tf.data_ptr() + 4 * D, D, D, (n + 1) * D)
     h7, col7, col7T = conv("conv7", h6.data_ptr(), dd, dd, n * dd)
@@ -1107,12 +1079,8 @@ def large_fov_forward(x: Tensor, W6: Tensor, W7: Tensor, W8: Tensor, dil: int, k
     n, dd, NC = h * w, W6.shape[0], W8.shape[0]
     tok = ops.zeros((B * n, C), x.device)
     ops.nchw_to_tokens_add(x, tok, B, n, C, skip_cls=False)
-    col6 = torch.empty((B * n, 9 * C), device=x.device, dtype=torch.float32)
-    ops.L().dupl_im2col_dil3(tok.data_ptr(), col6.data_ptr(), B, h, w, C, dil, C, n * C, ops._stream())
-    h6 = ops.linear(col6, W6.reshape(dd, -1), relu=True)
-    col7 = torch.empty((B * n, 9 * dd), device=x.device, dtype=torch.float32)
-    ops.L().dupl_im2col_dil3(h6.data_ptr(), col7.data_ptr(), B, h, w, dd, dil, dd, n * dd, ops._stream())
-    h7 = ops.linear(col7, W7.reshape(W7.shape[0], -1), relu=True)
+    h6, col6 = _conv_col32(tok.data_ptr(), x.device, B, h, w, C, dil, C, n * C, W6.reshape(dd, -1))
+    h7, col7 = _conv_col32(h6.data_ptr(), x.device, B, h, w, dd, dil, dd, n * dd, W7.reshape(W7.shape[0], -1))
     seg_tok = ops.linear(h7, W8.reshape(NC, -1))
     seg = ops.tokens_to_nchw(seg_tok, B, n, NC, h, w, skip_cls=False)
     if keep is not None:
@@ -1235,6 +1203,21 @@ def _linear_backward16(P: StudentParams, dy: Tensor, x: Tensor, name: str, dgelu
     return dx
 
 
+def _linear_backward(P: StudentParams, dy: Tensor, x: Tensor, x16, name: str, on_planes, *, dgelu_of: Optional[Tensor] = None,
+                     dx_feeds_split: bool = False, xT16=None, wT16=None, has_bias: bool = True,
+                     wgrads: Optional[list] = None) -> Tensor:
+    """Backward of the Linear `name` (y = x W^T + b): accumulates dW, db; returns dx (* gelu'(dgelu_of)).  It runs where the
+    forward ran -- same operands, same range verdict: k-major on the forward's planes x16 where the site ran on planes
+    (on_planes) and the forward kept them, on transposed planes where it kept none, on the exact-f32 kernels otherwise.
+    Each route ignores the arguments it has no use for (f32: nothing feeds a split; k-major: nothing is transposed)."""
+    if on_planes and x16 is not None:
+        return _linear_backward16_km(P, dy, x16, name, dgelu_of=dgelu_of, dx_feeds_split=dx_feeds_split, wgrads=wgrads)
+    if on_planes:
+        return _linear_backward16(P, dy, x, name, dgelu_of=dgelu_of, has_bias=has_bias, dx_feeds_split=dx_feeds_split,
+                                  xT16=xT16, wT16=wT16)
+    return _linear_backward32(P, dy, x, name, dgelu_of=dgelu_of, has_bias=has_bias)
+
+
 BLOCK_OPERANDS_MULTI = os.environ.get("DUPL_BLOCK_OPERANDS_MULTI", "1") != "0"
 
 
@@ -1307,13 +1290,11 @@ def network_backward(P: StudentParams, sv: HeadSaved, dcls: Optional[Tensor], ds
         def conv_bwd(site, dy, col, colT16, Cin, dx_ptr, ld, img_stride, accumulate, relu_of):
             """dW += dy^T col and dx (+)= col2im(dy W) [relu_of > 0] of one 3x3 conv."""
             name = f"decoder.{site}"
-            if not (f16 and guard[site]):
-                dcol, tc = _linear_backward32(P, dy, col, name, has_bias=False), False
-            else:
-                # tap-major data gradient: the same k-sums stored at column tap * Cin + c, which col2im reads in float4 runs
-                tc = bool(DECODER_PLANES & 2) and Cin % 4 == 0
-                dcol = _linear_backward16(P, dy, col, name, has_bias=False, xT16=colT16,
-                                          wT16=P.w16T_tc(name + ".weight", dd, Cin) if tc else None)
+            on_planes = bool(f16 and guard[site])
+            # tap-major data gradient: the same k-sums stored at column tap * Cin + c, which col2im reads in float4 runs
+            tc = on_planes and bool(DECODER_PLANES & 2) and Cin % 4 == 0
+            dcol = _linear_backward(P, dy, col, None, name, on_planes, has_bias=False, xT16=colT16,
+                                    wT16=P.w16T_tc(name + ".weight", dd, Cin) if tc else None)
             fn = ops.L().dupl_col2im_dil3_tc if tc else ops.L().dupl_col2im_dil3
             fn(dcol.data_ptr(), dx_ptr, B, h, w, Cin, dil, ld, img_stride, accumulate, relu_of, ops._stream())
 
@@ -1343,6 +1324,7 @@ def encoder_backward(P: StudentParams, enc: "EncoderSaved", dtf: Tensor, dta: Op
     dx = ops.layernorm_bwd(dtf, enc.x_last, W["encoder.norm.weight"], enc.mean_f, enc.rstd_f,
                            G["encoder.norm.weight"], G["encoder.norm.bias"], amax_for_next=f16 and gb[cfg.depth - 1]["fc2"])
     aux_idx = cfg.aux_layer % cfg.depth
+    no_planes = dict.fromkeys(RangeGuard.SITES, False)      # the verdicts of the exact-f32 mode: no site ran on planes
     Hh, hd = cfg.num_heads, cfg.head_dim
     scale = hd ** -0.5
     for i in reversed(range(cfg.depth)):
@@ -1351,42 +1333,29 @@ def encoder_backward(P: StudentParams, enc: "EncoderSaved", dtf: Tensor, dta: Op
         if dta is not None and i == aux_idx:
             ops.axpy_(dx, dta, 1.0)
             dx._dupl_amax = None         # modified after its producer took the max
-        g = gb[i] if f16 else None
-
-        def lin_bwd(site):      # the site's backward runs where its forward ran: same operands, same range verdict
-            return _linear_backward16 if (f16 and g[site]) else _linear_backward32
-
+        g = gb[i] if f16 else no_planes
         # the block's weight gradients (18 .. 72 tiles of 256 x 128 each) are collected and leave as ONE launch after its data
         # gradients: whole tiles over the whole token axis, no split-K, no atomics (ops.wgrad16_group)
         wg = [] if WGRAD_GROUP else None
-
-        def lin(site, dy_, x_, x16_, nm, **kw):
-            if f16 and g[site] and x16_ is not None:          # forward planes kept: k-major backward
-                return _linear_backward16_km(P, dy_, x16_, nm, dgelu_of=kw.get("dgelu_of"), dx_feeds_split=kw.get("dx_feeds_split", False),
-                                             wgrads=wg)
-            return lin_bwd(site)(P, dy_, x_, nm, **kw)
-
-        def feeds(site):        # does the tensor go into a scaled split next (= is `site`'s backward an f16x3 one)?
-            return {"dx_feeds_split": bool(g[site])} if f16 else {}
         att16 = f16 and s.qkv16 is not None and N <= 2048
+        # x^T planes of the sites that run on transposed planes, prepared in one launch
         xT = _block_operands16(P, p, s, g, D, D * cfg.mlp_ratio) if (f16 and BLOCK_OPERANDS_MULTI) else {}
-
-        def pre(site):          # x^T planes prepared above (f16x3 sites only)
-            return {"xT16": xT[site]} if site in xT else {}
-        # MLP
-        dpre1 = lin("fc2", dx, s.h1, s.h1_16, p + "mlp.fc2", dgelu_of=s.pre1, **(feeds("fc1") if g and g["fc2"] else {}), **pre("fc2"))
-        dln2 = lin("fc1", dpre1, s.ln2, s.ln2_16, p + "mlp.fc1", **pre("fc1"))
+        # MLP (dx_feeds_split: does dx go into a scaled split next = is its consumer's backward an f16x3 one?  fc1's and qkv's dx
+        # go to a LayerNorm backward)
+        dpre1 = _linear_backward(P, dx, s.h1, s.h1_16, p + "mlp.fc2", g["fc2"], dgelu_of=s.pre1, dx_feeds_split=bool(g["fc1"]),
+                                 xT16=xT.get("fc2"), wgrads=wg)
+        dln2 = _linear_backward(P, dpre1, s.ln2, s.ln2_16, p + "mlp.fc1", g["fc1"], xT16=xT.get("fc1"), wgrads=wg)
         del dpre1
         dx_mid = ops.layernorm_bwd(dln2, s.x_mid, W[p + "norm2.weight"], s.mean2, s.rstd2,
                                    G[p + "norm2.weight"], G[p + "norm2.bias"], dres=dx, amax_for_next=f16 and g["proj"])
         # attention
-        datt = lin("proj", dx_mid, s.att, s.att16, p + "attn.proj",
-                   **({"dx_feeds_split": bool(att16)} if g and g["proj"] else {}), **pre("proj"))
+        datt = _linear_backward(P, dx_mid, s.att, s.att16, p + "attn.proj", g["proj"], dx_feeds_split=bool(att16),
+                                xT16=xT.get("proj"), wgrads=wg)
         if att16:
             dqkv = ops.attention_bwd16(s.qkv16, s.att, datt, s.lse, B, N, Hh, hd, scale, amax_for_next=bool(g["qkv"]))
         else:
             dqkv = ops.attention_bwd(s.qkv, s.att, datt, s.lse, B, N, Hh, hd, scale)
-        dln1 = lin("qkv", dqkv, s.ln1, s.ln1_16, p + "attn.qkv", **pre("qkv"))
+        dln1 = _linear_backward(P, dqkv, s.ln1, s.ln1_16, p + "attn.qkv", g["qkv"], xT16=xT.get("qkv"), wgrads=wg)
         del dqkv, datt, xT
         dx = ops.layernorm_bwd(dln1, s.x_in, W[p + "norm1.weight"], s.mean1, s.rstd1,
                                G[p + "norm1.weight"], G[p + "norm1.bias"], dres=dx_mid,

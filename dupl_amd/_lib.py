@@ -108,6 +108,7 @@ class CamEvalDesc(ctypes.Structure):
 
 GEMM_A_MCONTIG, GEMM_B_NCONTIG, GEMM_GELU, GEMM_ACCUM = 1, 2, 4, 8
 GEMM_MUL_DGELU, GEMM_RELU, GEMM_MUL_RELUMASK, GEMM_ABS, GEMM_STORE_PRE = 16, 32, 64, 128, 256
+GEMM_C_FRESH = 512            # DUPL_GEMM_C_FRESH (dupl_gemm_f16x3_group)
 
 class SplitItem(ctypes.Structure):
     """dupl_split_item (include/dupl_hip.h)."""

@@ -436,7 +436,8 @@ __device__ __forceinline__ void epi16_quad(const dupl_gemm16_desc& p, const Epi1
 // side buffer, 8 rows x 64 columns at a time (4 WM passes: MFMA tile i, register group g = rows 8 g .. 8 g + 7 of it).
 // Same access pattern as gemm16_epilogue_lds (b32 writes of 32 consecutive floats, b128 reads of whole 256-byte rows ->
 // float4 global accesses); in-order LDS execution within the wave orders the passes.
-template <int WM, int WN, bool ACC = false, bool SINGLE = false, bool ATOM = true>
+// OVERW: the caller may ask for C = v in place of C += v (DUPL_GEMM_C_FRESH; the grouped whole-tile launch only)
+template <int WM, int WN, bool ACC = false, bool SINGLE = false, bool ATOM = true, bool OVERW = false>
 __device__ __forceinline__ void gemm16_epilogue_side(const dupl_gemm16_desc& p, f32x16 (&accM)[WM][WN],
                                                      f32x16 (&accX)[SINGLE ? 1 : WM][SINGLE ? 1 : WN],
                                                      float* __restrict__ side, const int mw, const int nw, const int lane,
@@ -486,7 +487,17 @@ __device__ __forceinline__ void gemm16_epilogue_side(const dupl_gemm16_desc& p, 
             if constexpr (ACC) {
                 // C += partial (stream-K pieces of a weight gradient meet in fp32 atomics): lane = column, one instruction adds
                 // to 64 consecutive floats of a row
-                if (nw + lane < p.N) {
+                if (OVERW && (p.flags & DUPL_GEMM_C_FRESH)) {
+                    // the owner of a whole tile over all of K, and C holds no value yet (a lazily zeroed gradient range): C = 0 + v,
+                    // the bits `C += v` leaves in a zero-filled C (the add keeps an underflowed -0 the +0 it would have become)
+                    if (nw + lane < p.N) {
+#pragma unroll
+                        for (int r = 0; r < 8; ++r) {
+                            const int row = mw + i * 32 + 8 * g + r;
+                            if (row < p.M) p.C[(size_t)row * p.ldc + nw + lane] = 0.f + side[r * 64 + lane];
+                        }
+                    }
+                } else if (nw + lane < p.N) {
 #pragma unroll
                     for (int r = 0; r < 8; ++r) {
                         const int row = mw + i * 32 + 8 * g + r;
@@ -1704,7 +1715,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
 #pragma unroll
             for (int s = 0; s < STAGES; ++s) issue(s);
         }
-        gemm16_epilogue_side<WM, WN, ACC != 0, true, ACC == 1>(p, acc, accX_unused, reinterpret_cast<float*>(smem + STAGES * STAGE) + wave * 512,
+        gemm16_epilogue_side<WM, WN, ACC != 0, true, ACC == 1, ONESHOT>(p, acc, accX_unused, reinterpret_cast<float*>(smem + STAGES * STAGE) + wave * 512,
                                                                mw, nw, lane, amx);
         if (!more) break;
     }
@@ -1808,8 +1819,9 @@ extern "C" int dupl_gemm_f16x3_group(const dupl_gemm16_desc* descs, int32_t n, d
     for (int i = 0; i < n; ++i) {
         const dupl_gemm16_desc& d = descs[i];
         if (!g16_operands_ok(d)) return DUPL_ERR_ARG;
-        // a weight gradient on the forward's planes: C += alpha A^T . B, both operands k-major, nothing else
-        if (d.flags != DUPL_GEMM_ACCUM || d.a_layout != 1 || d.b_layout != 1) return DUPL_ERR_ARG;
+        // a weight gradient on the forward's planes: C += alpha A^T . B, both operands k-major, nothing else (per problem with
+        // DUPL_GEMM_C_FRESH: C = that, the owner block does not read C)
+        if ((d.flags & ~DUPL_GEMM_C_FRESH) != DUPL_GEMM_ACCUM || d.a_layout != 1 || d.b_layout != 1) return DUPL_ERR_ARG;
         if (!d.C || d.C_hi || d.C_lo || d.bias || d.res || d.c_rows || d.amax_out) return DUPL_ERR_ARG;
         g.d[i] = d;
         g.first[i] = total;

@@ -409,6 +409,18 @@ __global__ void fill_kernel(float* p, float v, long n) {
     const long st = (long)gridDim.x * blockDim.x;
     for (; i < n; i += st) p[i] = v;
 }
+// p[lo .. hi) = v for every {lo, hi} of a device table: blockIdx.y = the range, the blocks of a row stride over it -- float4 stores
+// between the 16-byte boundaries of the range, single floats before and after
+__global__ void fill_ranges_kernel(float* p, float v, const long* __restrict__ ranges) {
+    const long lo = ranges[2 * blockIdx.y], hi = ranges[2 * blockIdx.y + 1];
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x, st = (long)gridDim.x * blockDim.x;
+    const long a = min(hi, lo + (long)((4 - ((reinterpret_cast<uintptr_t>(p + lo) >> 2) & 3)) & 3));     // first aligned element
+    const long n4 = (hi - a) >> 2, b = a + 4 * n4;
+    float4* q = reinterpret_cast<float4*>(p + a);
+    for (long i = t; i < n4; i += st) q[i] = make_float4(v, v, v, v);
+    if (t < a - lo) p[lo + t] = v;
+    if (t < hi - b) p[b + t] = v;
+}
 __global__ void axpy_kernel(float* y, const float* x, float a, long n) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long st = (long)gridDim.x * blockDim.x;
@@ -529,6 +541,16 @@ extern "C" int dupl_fill(float* p, float v, int64_t n, dupl_stream_t s) {
     if (!p || n < 0) return DUPL_ERR_ARG;
     if (n == 0) return DUPL_OK;
     DUPL_LAUNCH(fill_kernel, dim3(ew_grid(n)), dim3(256), 0, (hipStream_t)s, p, v, (long)n);
+    return dupl_launch_status();
+}
+extern "C" int dupl_fill_ranges(float* p, float v, const int64_t* ranges, int32_t n_ranges, dupl_stream_t s) {
+    if (!p || n_ranges < 0 || n_ranges > 65535 || (reinterpret_cast<uintptr_t>(p) & 3)) return DUPL_ERR_ARG;
+    if (n_ranges == 0) return DUPL_OK;                  // (an empty table may have no address)
+    if (!ranges || (reinterpret_cast<uintptr_t>(ranges) & 7)) return DUPL_ERR_ARG;
+    static_assert(sizeof(long) == sizeof(int64_t), "the table is read as long");
+    // 8 blocks per range = 8 192 floats per sweep: the caller lists a long range as pieces (FlatStorage: 32 768 floats, four
+    // float4 stores per thread), so that neither a bias-sized range costs a hundred idle blocks nor a conv weight runs on eight
+    DUPL_LAUNCH(fill_ranges_kernel, dim3(8, (unsigned)n_ranges), dim3(256), 0, (hipStream_t)s, p, v, reinterpret_cast<const long*>(ranges));
     return dupl_launch_status();
 }
 extern "C" int dupl_axpy(float* y, const float* x, float a, int64_t n, dupl_stream_t s) {

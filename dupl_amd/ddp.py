@@ -79,6 +79,7 @@ class GradReducer:
 
     def _issue(self, student: int, lo: int, hi: int):
         """all-reduce grad[lo:hi] in pieces of at most bucket_elems (returns immediately)."""
+        self.store.settle_grads(lo, hi)      # a lazily zeroed range this rank's backward never wrote goes out as zeros
         while lo < hi:
             n = min(self.bucket_elems, hi - lo)
             t = self.store.grad[lo:lo + n]

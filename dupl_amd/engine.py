@@ -210,6 +210,67 @@ class FlatStorage:
         self._w16T: Dict = {}
         self._w16F0: Dict = {}
         self.guard = RangeGuard(self)
+        # lazily zeroed gradient ranges (zero_grad(lazy=True)): the (student, key) whose range holds NO value yet -- its first writer
+        # overwrites it (ops.wgrad16_group fresh=) or fills it first (settle_key); every reader settles what is still fresh
+        self._fresh: set = set()
+        self._eager_table: Optional[Tensor] = None     # device table of the ranges zero_grad(lazy=True) does fill
+
+    # ---- lazily zeroed gradient ranges -----------------------------------------------------------------------------------------
+    LAZY_GRADS = ("attn.qkv.weight", "attn.proj.weight", "mlp.fc1.weight", "mlp.fc2.weight")
+
+    def lazy_keys(self) -> List[str]:
+        """The parameters whose gradient range a lazy zero_grad leaves unwritten: the Linear weights of every transformer block --
+        each receives exactly one weight gradient per backward pass, from a block that owns a whole tile over all of K."""
+        return [k for k in self.layout if k.startswith("encoder.blocks.") and k.endswith(self.LAZY_GRADS)]
+
+    def _abs_range(self, student: int, key: str) -> Tuple[int, int]:
+        off, n = self.layout[key]
+        return student * self.student_numel + off, student * self.student_numel + off + n
+
+    def zero_grad(self, lazy: bool = False):
+        """grad = 0 on the current stream.  lazy: one launch over everything BUT the lazy ranges, which are marked fresh instead."""
+        if not lazy:
+            ops.fill_(self.grad, 0.0)   # keep the .grad views alive: one fused fill
+            self._fresh.clear()
+            return
+        if self._eager_table is None or self._eager_table.device != self.grad.device:
+            lazy_r = sorted(self._abs_range(s, k) for s in range(self.n_students) for k in self.lazy_keys())
+            rows, cur = [], 0
+            for lo, hi in lazy_r:
+                if lo > cur:
+                    rows.append((cur, lo))
+                cur = hi
+            if cur < self.grad.numel():
+                rows.append((cur, self.grad.numel()))
+            # dupl_fill_ranges sweeps a range with 8 blocks: long ranges (patch embedding, heads, decoder convs) go in as pieces
+            piece = 32768
+            rows = [(a, min(a + piece, hi)) for lo, hi in rows for a in range(lo, hi, piece)]
+            self._eager_table = torch.tensor(rows, dtype=torch.int64).reshape(-1, 2).to(self.grad.device)
+        ops.fill_ranges_(self.grad, self._eager_table, 0.0)
+        self._fresh = {(s, k) for s in range(self.n_students) for k in self.lazy_keys()}
+
+    def take_fresh(self, student: int, key: str) -> bool:
+        """True once per fresh range: the caller OVERWRITES grad[key] now (the mark is cleared)."""
+        if (student, key) in self._fresh:
+            self._fresh.discard((student, key))
+            return True
+        return False
+
+    def settle_key(self, student: int, key: str):
+        """Before a writer that accumulates into grad[key]: a range that is still fresh is filled first."""
+        if self.take_fresh(student, key):
+            lo, hi = self._abs_range(student, key)
+            ops.fill_(self.grad[lo:hi], 0.0)
+
+    def settle_grads(self, lo: int = 0, hi: Optional[int] = None):
+        """Before a reader of grad[lo:hi) (absolute offsets; default: all of it): the fresh ranges that meet it become zeros."""
+        if not self._fresh:
+            return
+        hi = self.grad.numel() if hi is None else hi
+        for s, k in sorted(self._fresh):
+            a, b = self._abs_range(s, k)
+            if a < hi and lo < b:
+                self.settle_key(s, k)
 
     def wait_streams(self):
         """Make the current stream wait for everything queued on the student streams."""
@@ -1143,6 +1204,7 @@ def _linear_backward32(P: StudentParams, dy: Tensor, x: Tensor, name: str, dgelu
                        has_bias: bool = True) -> Tensor:
     """Backward of y = x W^T + b on the exact-f32 MFMA kernels: accumulates dW, db; returns dx (* gelu'(dgelu_of))."""
     N = dy.shape[1]
+    P.store.settle_key(P.student, name + ".weight")
     ops.linear_wgrad(dy, x, P.g[name + ".weight"], accumulate=True)
     if has_bias:
         ops.colsum(dy, P.g[name + ".bias"], accumulate=True)
@@ -1164,7 +1226,9 @@ def _linear_backward16_km(P: StudentParams, dy: Tensor, x16, name: str, dgelu_of
     if wgrads is not None:
         # the weight gradient joins the block's grouped launch (network_backward: ops.wgrad16_group); dy16 stays alive until then
         wgrads.append((dy16, x16, gw.view(N, -1), alpha))
+        wgrads.keys.append(name + ".weight")
     else:
+        P.store.settle_key(P.student, name + ".weight")
         _lin16(P, dy16, x16, out=gw.view(N, -1), accumulate=True, alpha=alpha, a_kmajor=True, b_kmajor=True, k_pad=Kp)
     if not fuse_bias:
         ops.colsum(dy, P.g[name + ".bias"], accumulate=True)
@@ -1193,6 +1257,7 @@ def _linear_backward16(P: StudentParams, dy: Tensor, x: Tensor, name: str, dgelu
     if xT16 is None:         # (the transformer blocks prepare x^T and W^T of all four Linears in one launch: _block_operands16)
         _, xT16, _ = ops.split_prepare(x, scaled=False, want_rm=False, want_T=True, rows_pad=Mp)
     gw = P.g[name + ".weight"]
+    P.store.settle_key(P.student, name + ".weight")
     _lin16(P, dyT16, xT16, out=gw.view(N, -1), accumulate=True, alpha=alpha)
     if has_bias and not fuse_bias:
         ops.colsum(dy, P.g[name + ".bias"], accumulate=True)
@@ -1219,6 +1284,14 @@ def _linear_backward(P: StudentParams, dy: Tensor, x: Tensor, x16, name: str, on
 
 
 BLOCK_OPERANDS_MULTI = os.environ.get("DUPL_BLOCK_OPERANDS_MULTI", "1") != "0"
+
+
+class _WGradGroup(list):
+    """The items of one transformer block's grouped weight-gradient launch (ops.wgrad16_group), with the parameter key of each."""
+
+    def __init__(self):
+        super().__init__()
+        self.keys: List[str] = []
 
 
 def _block_operands16(P: StudentParams, p: str, s: "BlockSaved", g: dict, D: int, Hd: int) -> dict:
@@ -1336,7 +1409,7 @@ def encoder_backward(P: StudentParams, enc: "EncoderSaved", dtf: Tensor, dta: Op
         g = gb[i] if f16 else no_planes
         # the block's weight gradients (18 .. 72 tiles of 256 x 128 each) are collected and leave as ONE launch after its data
         # gradients: whole tiles over the whole token axis, no split-K, no atomics (ops.wgrad16_group)
-        wg = [] if WGRAD_GROUP else None
+        wg = _WGradGroup() if WGRAD_GROUP else None
         att16 = f16 and s.qkv16 is not None and N <= 2048
         # x^T planes of the sites that run on transposed planes, prepared in one launch
         xT = _block_operands16(P, p, s, g, D, D * cfg.mlp_ratio) if (f16 and BLOCK_OPERANDS_MULTI) else {}
@@ -1363,7 +1436,8 @@ def encoder_backward(P: StudentParams, enc: "EncoderSaved", dtf: Tensor, dta: Op
         if wg:
             # (measured and dropped: this launch on a side stream of its student, to share the chip with the narrow data-gradient
             # launches of the next block -- 55.2 vs 54.4 ms at 4 img/GPU, 33.8 vs 32.6 at 2, same box: DESIGN 6)
-            ops.wgrad16_group(wg, tuning=P.store.gemm16_tuning)
+            # a range no one has written since a lazy zero_grad is overwritten (and is fresh no more): a second backward accumulates
+            ops.wgrad16_group(wg, tuning=P.store.gemm16_tuning, fresh=[P.store.take_fresh(P.student, k) for k in wg.keys])
         del wg
         enc.blocks[i] = None  # release activations as we go
         if on_ready is not None:

@@ -401,12 +401,15 @@ def linear16(x, W: Split16, bias: Optional[Tensor] = None, *, gelu: bool = False
     return y, y16
 
 
-def wgrad16_group(items, tuning: Optional[dict] = None):
+def wgrad16_group(items, tuning: Optional[dict] = None, fresh=None):
     """Several weight gradients dW_i += alpha_i dy_i^T x_i in ONE launch (dupl_gemm_f16x3_group: a whole 256 x 128 tile per block over
     the whole token axis, no split-K, no atomics -- the same bits in deterministic mode).  items: [(dy16 Split16 [Kp, n_out] scaled
-    format 1 planes with zero rows up to Kp, x16 Split16 / view [rows, n_in] format 1 planes, out fp32 [n_out, n_in], alpha)]."""
+    format 1 planes with zero rows up to Kp, x16 Split16 / view [rows, n_in] format 1 planes, out fp32 [n_out, n_in], alpha)].
+    fresh: one bool per item -- True: `out` holds no value yet (a lazily zeroed gradient range): dW_i = ..., written without being
+    read, the bits of the accumulating form into zeros (DUPL_GEMM_C_FRESH)."""
     descs = []
-    for dy16, x16, out, alpha in items:
+    assert fresh is None or len(fresh) == len(items)
+    for j, (dy16, x16, out, alpha) in enumerate(items):
         assert dy16.fmt == 1 and getattr(x16, "fmt", 0) == 1, "grouped weight gradients read format 1 planes k-major"
         Kp = dy16.rows
         assert Kp % 32 == 0 and Kp >= 96 and out.is_contiguous() and out.shape == (dy16.cols, x16.cols)
@@ -418,7 +421,7 @@ def wgrad16_group(items, tuning: Optional[dict] = None):
         d.C = out.data_ptr()
         d.M, d.N, d.K = dy16.cols, x16.cols, Kp
         d.lda, d.ldb, d.ldc, d.ldo = dy16.cols, x16.cols, out.stride(0), x16.cols
-        d.flags = _lib.GEMM_ACCUM
+        d.flags = _lib.GEMM_ACCUM | (_lib.GEMM_C_FRESH if fresh is not None and fresh[j] else 0)
         d.alpha_dev = int(alpha) if alpha is not None else None
         d.fmt, d.post_scale = 1, 2.0 ** -(getattr(dy16, "exp", 0) + getattr(x16, "exp", 0))
         d.a_layout, d.b_layout = 1, 1
@@ -859,6 +862,13 @@ def to_device_async(host, dtype, device) -> Tensor:
 
 def fill_(t: Tensor, v: float):
     L().dupl_fill(t.data_ptr(), float(v), t.numel(), _stream())
+    return t
+
+
+def fill_ranges_(t: Tensor, table: Tensor, v: float = 0.0):
+    """t[lo:hi] = v for every row {lo, hi} of `table` (int64 [n, 2] on t's device, elements of the flat t) in one launch."""
+    assert table.dtype == torch.int64 and table.dim() == 2 and table.shape[1] == 2 and table.is_contiguous() and table.device == t.device
+    L().dupl_fill_ranges(t.data_ptr(), float(v), table.data_ptr(), table.shape[0], _stream())
     return t
 
 

@@ -216,7 +216,12 @@ def compute_losses(model, par, inputs, cls_label, img_box, n_iter: int, args: St
 def train_step(model, optim, par, inputs, cls_label, img_box, n_iter: int, args: StepArgs, cls_label_host=None,
                inputs_aug=None):
     """zero_grad -> losses -> backward -> optimiser step (train_final_voc.py:470-472)."""
-    optim.zero_grad()
+    # (the block Linear weights' gradient ranges are overwritten by their one weight gradient instead of zeroed and re-read: nothing
+    # between here and step() writes into the .grad views by hand)
+    if hasattr(optim, "begin_step"):
+        optim.zero_grad(lazy=True)
+    else:
+        optim.zero_grad()
     loss, out = compute_losses(model, par, inputs, cls_label, img_box, n_iter, args, cls_label_host, inputs_aug)
     if hasattr(optim, "begin_step"):
         optim.begin_step(model)       # the update of each gradient range is issued as the backward pass (+ exchange) finalises it

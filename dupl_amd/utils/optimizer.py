@@ -142,6 +142,7 @@ class PolyWarmupAdamW(torch.optim.Optimizer):
         store, m, v, steps = self._flat
         arm = self._armed
         base = s * store.student_numel
+        store.settle_grads(lo, hi)       # (a lazily zeroed range the backward pass never wrote)
         for a_, b_ in arm["done"][s]:
             if a_ < hi and lo < b_:
                 raise RuntimeError("PolyWarmupAdamW: a gradient range came back final twice between begin_step() and step() -- "
@@ -185,11 +186,14 @@ class PolyWarmupAdamW(torch.optim.Optimizer):
                 if trig == event:
                     self._update_range(s, lo, hi)
 
-    def zero_grad(self, set_to_none: bool = False):
+    def zero_grad(self, set_to_none: bool = False, lazy: bool = False):
+        """lazy (trainer.train_step): the gradient ranges of the transformer blocks' Linear weights are not filled -- the one weight
+        gradient each receives in a backward pass overwrites it (FlatStorage.zero_grad); whoever else writes or reads such a range
+        before that settles it to zeros first.  The default fills everything: a caller may write into the .grad views next."""
         self._disarm()       # a step that was armed but never taken (backward raised, non-finite loss skipped): nothing stays hooked
         if self._flat is not None:
             self._flat[0].wait_streams()
-            ops.fill_(self._flat[0].grad, 0.0)   # keep the .grad views alive: one fused fill
+            self._flat[0].zero_grad(lazy=lazy)
         else:
             super().zero_grad(set_to_none=False)
 
@@ -212,6 +216,7 @@ class PolyWarmupAdamW(torch.optim.Optimizer):
                                "parameter buffer with fused HIP launches (no per-tensor fallback)")
         store, m, v, steps = self._flat
         store.wait_streams()     # the students' backward passes may still be running on their own streams
+        store.settle_grads()     # lazily zeroed ranges that no backward pass wrote read as zeros
         # a student whose operand planes are current gets them rewritten by the update itself (no split pass over the weights
         # before the next forward); segments without gradients keep their values, hence their planes
         arm = self._disarm()
@@ -257,6 +262,7 @@ class PolyWarmupAdamW(torch.optim.Optimizer):
         if self._flat is not None:
             store, m, v, steps = self._flat
             store.wait_streams()
+            store.settle_grads()      # (what is saved next to this state, or read after it, sees zeros, not an unwritten range)
             sd.update(exp_avg=m.detach().clone(), exp_avg_sq=v.detach().clone(), steps=[list(r) for r in steps],
                       seg_has_grad=[list(r) for r in store.seg_has_grad])
         return sd

@@ -57,6 +57,8 @@ int dupl_build_digest(char* out, int32_t cap);
 #define DUPL_GEMM_MUL_RELUMASK 64 /* v *= (aux[m][n] > 0)   (ReLU backward; aux = post-ReLU output) */
 #define DUPL_GEMM_ABS 128       /* v = |v|  (PTC cosine matrix) */
 #define DUPL_GEMM_STORE_PRE 256 /* also WRITE the pre-activation (alpha*acc+bias) to aux[m][n] (training forward of fc1) */
+#define DUPL_GEMM_C_FRESH 512   /* dupl_gemm_f16x3_group only, next to DUPL_GEMM_ACCUM: C holds no value yet -- C = v, C is not read; the
+                                   bits are those of C += v into a zero-filled C */
 typedef struct dupl_gemm_desc {
     uint32_t struct_size;  /* sizeof(dupl_gemm_desc) of the caller's header; a mismatch is refused */
     int32_t tile_rows;     /* launch tuning, per call (0 = heuristic): row tile 64 / 128 */
@@ -146,7 +148,9 @@ int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream);
 /* n (<= DUPL_GEMM16_GROUP_MAX) independent weight gradients C_i += alpha_i A_i^T . B_i (every descriptor: fmt 1, a_layout = b_layout = 1,
  * flags = DUPL_GEMM_ACCUM) as ONE launch, a whole 256 x 128 tile per block over all of K: the four dW of a transformer block
  * (autograd of vit.py:92-136: 18 .. 72 tiles each) fill the chip together, nothing is split along K and nothing meets in atomics --
- * bit-reproducible with and without dupl_set_deterministic.  descs: HOST array (copied into the launch). */
+ * bit-reproducible with and without dupl_set_deterministic.  descs: HOST array (copied into the launch).
+ * Per descriptor, flags = DUPL_GEMM_ACCUM | DUPL_GEMM_C_FRESH: C_i = alpha_i A_i^T . B_i, written once and never read (a gradient
+ * range nobody has zeroed: dupl_fill_ranges) -- the same bits as the accumulating form into zeros. */
 #define DUPL_GEMM16_GROUP_MAX 8
 int dupl_gemm_f16x3_group(const dupl_gemm16_desc* descs, int32_t n, dupl_stream_t stream);
 /* the operand split of the GEMM above: n fp32 values (n % 4 == 0) -> hi / lo fp16 planes (no reference counterpart) */
@@ -505,6 +509,11 @@ int dupl_adamw(float* p, float* g, float* m, float* v, int64_t n, float lr, floa
                dupl_stream_t s);
 /* optimizer.zero_grad() (train_final_voc.py:470) and buffer initialisation: p[0..n) = v */
 int dupl_fill(float* p, float v, int64_t n, dupl_stream_t s);
+/* the same over a LIST of ranges as one launch: p[lo_i .. hi_i) = v for i < n_ranges; ranges = n_ranges {int64 lo, int64 hi} pairs
+ * (elements relative to p, lo <= hi) in DEVICE memory; n_ranges = 0 is a no-op (ranges may be NULL then).  Every range is swept
+ * by 8 blocks of 256 threads: list a long range as pieces of a few ten thousand elements.  zero_grad() of the flat gradient buffer without the ranges whose first
+ * writer of the step overwrites them (DUPL_GEMM_C_FRESH); the caller builds the table once per model. */
+int dupl_fill_ranges(float* p, float v, const int64_t* ranges, int32_t n_ranges, dupl_stream_t s);
 /* y += a*x: the aux-branch gradient joining the residual stream (autograd of vit.py:316-326) */
 int dupl_axpy(float* y, const float* x, float a, int64_t n, dupl_stream_t s);
 /* y *= a: DDP's division of the all-reduced gradients by the world size (train_final_voc.py:155) */

@@ -43,6 +43,27 @@ def sha(t) -> str:
     return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()[:16]
 
 
+def settled_grad(model):
+    """The flat gradient buffer as a reader must see it: ranges a lazy zero_grad left unwritten read as zeros (a tree without lazy
+    ranges has nothing to settle)."""
+    store = model.flat_storage
+    if hasattr(store, "settle_grads"):
+        store.settle_grads()
+        torch.cuda.synchronize()
+    return store.grad
+
+
+def zero_grad(model):
+    """What trainer.train_step's zero_grad leaves: where the tree zeroes lazily, the lazy ranges hold NaN, so that a range nobody
+    overwrote or settled shows in the digest."""
+    store = model.flat_storage
+    if hasattr(store, "zero_grad"):
+        store.grad.fill_(float("nan"))
+        store.zero_grad(lazy=True)
+    else:
+        store.grad.zero_()
+
+
 def build(backbone, cfg, dev):
     model = siamese_network(backbone, num_classes=21, pretrained=False, aux_layer=-3)
     model.load_state_dict(O.make_siamese_params(cfg, 21, seed=5), strict=True)
@@ -55,14 +76,14 @@ def step(backbone, cfg, B, S, dev):
     model = build(backbone, cfg, dev)
     par = PAR(num_iter=10, dilations=[1, 2, 4, 8, 12, 24]).to(dev)
     inputs, cls_label, img_box = O.synthetic_batch(B, 20, S, seed=11)
-    model.flat_storage.grad.zero_()
+    zero_grad(model)
     loss, out = trainer.compute_losses(model, par, inputs.to(dev), cls_label.to(dev), img_box, 5000, trainer.StepArgs(),
                                        cls_label_host=cls_label)
     loss.sum().backward()
     model.flat_storage.wait_streams()
     torch.cuda.synchronize()
     d = {k: sha(out[k]) for k in KEEP}
-    d["grad"] = sha(model.flat_storage.grad)
+    d["grad"] = sha(settled_grad(model))
     return d
 
 
@@ -79,14 +100,14 @@ def eval_paths(dev):
         for name, t in zip(("cam_aux_1", "cam_1", "cam_aux_2", "cam_2"), model(x, cam_only=True)):
             d[name] = sha(t)
         d["decoder"] = sha(model.branch1.decoder(model(x, val=True, branch=1)[2]))
-    model.flat_storage.grad.zero_()
+    zero_grad(model)
     outs = model.branch1.encoder(x)
     R = [O.hash_normal(f"rf{i}", tuple(o.shape), seed=2).to(dev) for i, o in enumerate(outs)]
     sum((o * r).sum() for o, r in zip(outs, R)).backward()
     torch.cuda.synchronize()
     for name, t in zip(("ff.cls", "ff.tokens", "ff.aux"), outs):
         d[name] = sha(t)
-    d["ff.grad"] = sha(model.flat_storage.grad)
+    d["ff.grad"] = sha(settled_grad(model))
     return d
 
 

@@ -106,6 +106,20 @@ class CamEvalDesc(ctypes.Structure):
         self.struct_size = ctypes.sizeof(CamEvalDesc)
 
 
+class SegEnsembleDesc(ctypes.Structure):
+    """Mirror of `dupl_seg_ensemble_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("C", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+        ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+        ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("gt", ctypes.c_void_p),
+        ("hist", ctypes.c_void_p), ("counts", ctypes.c_void_p), ("pred", ctypes.c_void_p), ("prob", ctypes.c_void_p),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(SegEnsembleDesc)
+
+
 GEMM_A_MCONTIG, GEMM_B_NCONTIG, GEMM_GELU, GEMM_ACCUM = 1, 2, 4, 8
 GEMM_MUL_DGELU, GEMM_RELU, GEMM_MUL_RELUMASK, GEMM_ABS, GEMM_STORE_PRE = 16, 32, 64, 128, 256
 GEMM_C_FRESH = 512            # DUPL_GEMM_C_FRESH (dupl_gemm_f16x3_group)
@@ -127,6 +141,7 @@ ATTN_SEGS_MAX = 4             # DUPL_ATTN_SEGS_MAX
 SPLIT_MULTI_MAX = 16
 GEMM16_GROUP_MAX = 8          # DUPL_GEMM16_GROUP_MAX
 CAM_EVAL_MAX_T, CAM_EVAL_MAX_C = 64, 255      # DUPL_CAM_EVAL_MAX_T, DUPL_CAM_EVAL_MAX_C
+SEG_ENSEMBLE_MAX_C = 255      # DUPL_SEG_ENSEMBLE_MAX_C
 
 _PROTO = re.compile(r"^\s*int\s+(dupl_\w+)\s*\(([^;{]*)\)\s*;", re.M | re.S)
 
@@ -145,6 +160,8 @@ def _ctype(decl: str):
         return ctypes.POINTER(CrfDesc)
     if "dupl_cam_eval_desc" in d:
         return ctypes.POINTER(CamEvalDesc)
+    if "dupl_seg_ensemble_desc" in d:
+        return ctypes.POINTER(SegEnsembleDesc)
     if "*" in d or d.startswith("dupl_stream_t"):
         return ctypes.c_void_p
     base = d.replace("const", "").split()

@@ -1,0 +1,336 @@
+// Ensemble of the two students at evaluation time (tools/eval_seg --ensemble 1; beyond the reference, which scores each student alone):
+// per output pixel the bilinear up-sampling of both students' accumulated logits, their softmax over the channels, the mean of the two
+// probability vectors, and the argmax of each student and of the mean -- ONE pass over the (H,W) label grid that also accumulates the
+// three confusion matrices and the two agreement counters.  The up-sampled logits and the per-student probabilities live in registers
+// only; composed from resize_bilinear, softmax, argmax_channels and confusion_accum the same result moves two (C,H,W) fp32 maps through
+// HBM four times.  Floor: one read of both students' logits + 8 B/px of gt + what is asked for (8 B/px pred, 4 C B/px prob).
+//   identity (VOC: the logits are already at label size): a thread reads its pixel's 2 C values straight from HBM -- once, kept in
+//     registers, when C <= 24; channel by channel in three sweeps (maximum, partition sum, mean) beyond;
+//   up-sampling (COCO: 28 x 28 logits, 254 KB per student, L2-resident): a workgroup owns a 64 x 4 output tile and stages the few
+//     source pixels under it (x C x 2 students) in LDS, channel-fastest, so a tap is one 16-byte LDS read per 4 channels; the channel
+//     loop runs twice (maximum + partition sum, then the mean).  Where the footprint does not fit (down-sampling) the taps are read
+//     through L1, channel by channel.
+// Histograms: 3 C^2 counters of 16 bits privatised per workgroup in LDS where they fit 40 KB (C <= 82) and flushed with 64-bit atomics,
+// otherwise 64-bit atomics straight to hist.  Integer atomics only: the result is bit-reproducible in either mode.
+#include "common.h"
+#include "../../include/dupl_hip.h"
+
+namespace {
+
+constexpr int SE_THREADS = 256;
+constexpr int SE_TW = 64, SE_TH = 4;     // output tile: a wave per row segment, 256 contiguous bytes per channel of prob
+constexpr int SE_BINS = 20480;           // 16-bit counters, two to a word (40 KB): 3 * 82^2 = 20172
+constexpr int SE_STAGE = 6144;           // floats of staged source pixels (24 KB): COCO 84 x 2 x (3 x 5) = 2520
+constexpr int SE_BLOCK_TILES = 255;      // tiles per workgroup at most: 255 * 256 pixels cannot overflow a 16-bit counter
+
+// The students' predictions must be the bits of upsample_argmax_kernel (eval.hip), so the source index and the tap are that kernel's
+// arithmetic with every rounding pinned to what hipcc makes of it there: r = fma(scale, o + 0.5, -0.5);
+// v = hy * (hx a + lx b) + ly * (hx c + lx d) with top = fma(hx, a, lx b), bot = fma(hx, c, lx d) and a plain hy top + ly bot.
+__device__ __forceinline__ void se_src(int o, float scale, int in, int& i0, int& i1, float& l1) {
+#pragma clang fp contract(off)
+    const float r = fmaxf(__builtin_fmaf(scale, (float)o + 0.5f, -0.5f), 0.f);
+    i0 = (int)r;
+    if (i0 > in - 1) i0 = in - 1;
+    i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+    l1 = r - (float)i0;
+}
+__device__ __forceinline__ float se_tap(float a, float b, float c, float d, float ly, float lx) {
+#pragma clang fp contract(off)
+    const float hy = 1.f - ly, hx = 1.f - lx;
+    const float top = __builtin_fmaf(hx, a, lx * b);
+    const float bot = __builtin_fmaf(hx, c, lx * d);
+    const float t = hy * top, u = ly * bot;
+    return t + u;
+}
+
+struct SegEnsArgs {
+    const float* a;
+    const float* b;
+    const long long* gt;
+    unsigned long long* hist;
+    unsigned long long* counts;
+    long long* pred;
+    float* prob;
+    int C, h, w, H, W;
+    int priv;            // histograms privatised in LDS
+    int bin_words;       // words of LDS in front of the stage
+    int stage_cap;       // floats of stage (0: every tap through L1)
+    int tiles_x, ntiles;
+};
+
+// exp(x) for x <= 0 as one v_exp_f32: the relative error grows with |x| ((|x| + 1) * 6e-8), the value shrinks as exp(x): no
+// probability is off by more than 1e-7 (tests: prob against float64, beside the composed fp32 path)
+__device__ __forceinline__ float se_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
+
+constexpr int SE_SMALL = 24;             // identity: channels a thread keeps in registers -- one read of the logits (VOC: 21)
+
+// Identity, C <= SE_SMALL (the VOC form).  r1 / r2: channel 0 of the wave's row segment (the same for all lanes: the loads take a
+// scalar base and the lane as offset, so SE_SMALL of them per student are in flight without an address register each).  Both
+// students' values are read ONCE and stay in registers through maximum, partition sum and mean: one exp per value.
+__device__ __forceinline__ void se_pixel_regs(const float* __restrict__ r1, const float* __restrict__ r2, int lane, int C,
+                                              float* __restrict__ prow, long HW, int& b1, int& b2, int& be) {
+    float u1[SE_SMALL], u2[SE_SMALL];
+#pragma unroll
+    for (int j = 0; j < SE_SMALL; ++j) {       // channels past C read as -inf: exp gives 0 and no argmax takes them
+        u1[j] = j < C ? r1[(long)j * HW + lane] : -INFINITY;
+        u2[j] = j < C ? r2[(long)j * HW + lane] : -INFINITY;
+    }
+    float m1 = -INFINITY, m2 = -INFINITY;
+    b1 = 0; b2 = 0;
+#pragma unroll
+    for (int j = 0; j < SE_SMALL; ++j) {
+        if (u1[j] > m1) { m1 = u1[j]; b1 = j; }
+        if (u2[j] > m2) { m2 = u2[j]; b2 = j; }
+    }
+    double s1 = 0.0, s2 = 0.0;                 // the partition sums in float64: the channel sums of e stay within rounding of 1
+#pragma unroll
+    for (int j = 0; j < SE_SMALL; ++j) {
+        u1[j] = se_exp(u1[j] - m1);
+        u2[j] = se_exp(u2[j] - m2);
+        s1 += (double)u1[j];
+        s2 += (double)u2[j];
+    }
+    const float h1 = 0.5f / (float)s1, h2 = 0.5f / (float)s2;          // e = (p1 + p2) / 2 = ex1 * (0.5 / s1) + ex2 * (0.5 / s2)
+    float me = -INFINITY;
+    be = 0;
+#pragma unroll
+    for (int j = 0; j < SE_SMALL; ++j) {
+        const float e = fmaf(u1[j], h1, u2[j] * h2);
+        if (e > me) { me = e; be = j; }
+        if (prow && j < C) prow[(long)j * HW + lane] = e;
+    }
+}
+
+// Up-sampling from the staged footprint.  The stage holds, per source pixel, student 1's Cp channels and then student 2's (Cp = C
+// rounded up to 4, the pad is 0): a tap is one 16-byte LDS read per 4 channels, and the four taps of a pixel need one address each.
+// t00 .. t11: float index of the four source pixels.  The channel loop runs twice, 4 channels at a time: first the maximum and the
+// partition sum together (the running sum is rescaled when a chunk raises the maximum), then the mean of the two probability
+// vectors and its argmax.
+__device__ __forceinline__ void se_chunk(const float* st, int t00, int t01, int t10, int t11, int c0, int C, float ly, float lx,
+                                         float (&u)[4]) {
+    const f32x4 A = *reinterpret_cast<const f32x4*>(st + t00 + c0), B = *reinterpret_cast<const f32x4*>(st + t01 + c0);
+    const f32x4 Cc = *reinterpret_cast<const f32x4*>(st + t10 + c0), D = *reinterpret_cast<const f32x4*>(st + t11 + c0);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) u[k] = c0 + k < C ? se_tap(A[k], B[k], Cc[k], D[k], ly, lx) : -INFINITY;
+}
+__device__ __forceinline__ void se_pixel_lds(const float* st, int Cp, int t00, int t01, int t10, int t11, float ly, float lx, int C,
+                                             float* prob, long HW, int& b1, int& b2, int& be) {
+    float m1 = -INFINITY, m2 = -INFINITY;
+    double s1 = 0.0, s2 = 0.0;
+    b1 = 0; b2 = 0;
+#pragma unroll 2
+    for (int c0 = 0; c0 < C; c0 += 4) {
+        float u1[4], u2[4];
+        se_chunk(st, t00, t01, t10, t11, c0, C, ly, lx, u1);
+        se_chunk(st + Cp, t00, t01, t10, t11, c0, C, ly, lx, u2);
+        const float o1 = m1, o2 = m2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (u1[k] > m1) { m1 = u1[k]; b1 = c0 + k; }
+            if (u2[k] > m2) { m2 = u2[k]; b2 = c0 + k; }
+        }
+        float a1 = 0.f, a2 = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            a1 += se_exp(u1[k] - m1);
+            a2 += se_exp(u2[k] - m2);
+        }
+        s1 = s1 * (double)se_exp(o1 - m1) + (double)a1;                 // first chunk: o = -inf, the factor is 0
+        s2 = s2 * (double)se_exp(o2 - m2) + (double)a2;
+    }
+    const float h1 = 0.5f / (float)s1, h2 = 0.5f / (float)s2;
+    float me = -INFINITY;
+    be = 0;
+#pragma unroll 2
+    for (int c0 = 0; c0 < C; c0 += 4) {
+        float u1[4], u2[4];
+        se_chunk(st, t00, t01, t10, t11, c0, C, ly, lx, u1);
+        se_chunk(st + Cp, t00, t01, t10, t11, c0, C, ly, lx, u2);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float e = fmaf(se_exp(u1[k] - m1), h1, se_exp(u2[k] - m2) * h2);
+            if (e > me) { me = e; be = c0 + k; }
+            if (prob && c0 + k < C) prob[(long)(c0 + k) * HW] = e;
+        }
+    }
+}
+
+// Everything else (identity with more channels, a footprint too large to stage: down-sampling), channel by channel through L1 / L2:
+// maximum, partition sum, mean.  IDENT: q points at the pixel itself, channel stride ps; otherwise at channel 0 of the source, ps the
+// plane stride and o00 .. o11 the four taps inside a plane.
+template <bool IDENT>
+__device__ __forceinline__ void se_pixel_any(const float* q1, const float* q2, long ps, int o00, int o01, int o10, int o11, float ly,
+                                             float lx, int C, float* prob, long HW, int& b1, int& b2, int& be) {
+    auto val = [&](const float* q, int c) -> float {
+        const float* p = q + (long)c * ps;
+        if (IDENT) return p[0];
+        return se_tap(p[o00], p[o01], p[o10], p[o11], ly, lx);
+    };
+    float m1 = -INFINITY, m2 = -INFINITY;
+    b1 = 0; b2 = 0;
+    for (int c = 0; c < C; ++c) {
+        const float u1 = val(q1, c), u2 = val(q2, c);
+        if (u1 > m1) { m1 = u1; b1 = c; }
+        if (u2 > m2) { m2 = u2; b2 = c; }
+    }
+    double s1 = 0.0, s2 = 0.0;
+    for (int c = 0; c < C; ++c) {
+        s1 += (double)se_exp(val(q1, c) - m1);
+        s2 += (double)se_exp(val(q2, c) - m2);
+    }
+    const float h1 = 0.5f / (float)s1, h2 = 0.5f / (float)s2;
+    float me = -INFINITY;
+    be = 0;
+    for (int c = 0; c < C; ++c) {
+        const float e = fmaf(se_exp(val(q1, c) - m1), h1, se_exp(val(q2, c) - m2) * h2);
+        if (e > me) { me = e; be = c; }
+        if (prob) prob[(long)c * HW] = e;
+    }
+}
+
+__global__ __launch_bounds__(SE_THREADS) void seg_ens_kernel(const SegEnsArgs a) {
+    extern __shared__ __align__(16) unsigned int se_lds[];
+    unsigned int* bins32 = se_lds;
+    float* st = reinterpret_cast<float*>(se_lds + a.bin_words);          // bin_words is a multiple of 4: 16-byte aligned
+    const int tid = threadIdx.x, C = a.C, H = a.H, W = a.W, h = a.h, w = a.w;
+    const int lane = tid & 63, wrow = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int nb = 3 * C * C, Cp = (C + 3) & ~3;
+    const bool want_hist = a.hist != nullptr, want_cnt = a.counts != nullptr;
+    const bool priv = want_hist && a.priv;
+    if (priv) {
+        for (int i = tid; i < (nb + 1) / 2; i += SE_THREADS) bins32[i] = 0u;
+        __syncthreads();
+    }
+    const bool ident = h == H && w == W;       // as torch: the same size is a copy, nothing is interpolated
+    const float sy = bil_scale(h, H, false), sx = bil_scale(w, W, false);
+    const long HW = (long)H * W, hw = (long)h * w;
+    int n_valid = 0, n_agree = 0;
+    for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+        const int ty0 = (t / a.tiles_x) * SE_TH, tx0 = (t % a.tiles_x) * SE_TW;
+        const int x = tx0 + lane, y = ty0 + wrow;
+        const bool live = x < W && y < H;
+        int fy0 = 0, fx0 = 0, fh = 0, fw = 0;
+        bool staged = false;
+        if (!ident) {
+            // the source pixels under this tile: the index is monotone in the output coordinate, so the first row's y0 and the last
+            // row's y1 bound every tap of the tile (the same for the columns); the same for every thread of the workgroup
+            int i1, j0;
+            float l;
+            const int ty1 = ty0 + SE_TH - 1 < H ? ty0 + SE_TH - 1 : H - 1, tx1 = tx0 + SE_TW - 1 < W ? tx0 + SE_TW - 1 : W - 1;
+            se_src(ty0, sy, h, fy0, i1, l);
+            se_src(ty1, sy, h, j0, i1, l);
+            fh = i1 - fy0 + 1;
+            se_src(tx0, sx, w, fx0, i1, l);
+            se_src(tx1, sx, w, j0, i1, l);
+            fw = i1 - fx0 + 1;
+            staged = (long)fh * fw * 2 * Cp <= (long)a.stage_cap;
+            __syncthreads();                   // the previous tile's taps are read
+            if (staged) {
+                // read in source order (consecutive threads on consecutive columns), written channel-fastest
+                const int plane = fh * fw, n = 2 * Cp * plane;
+                for (int i = tid; i < n; i += SE_THREADS) {
+                    const int pc = i / plane, rq = i - pc * plane, r = rq / fw, q = rq - r * fw;
+                    const int sidx = pc >= Cp ? 1 : 0, c = pc - sidx * Cp;
+                    const float* src = (sidx ? a.b : a.a) + (long)c * hw;
+                    st[(rq * 2 + sidx) * Cp + c] = c < C ? src[(long)(fy0 + r) * w + fx0 + q] : 0.f;
+                }
+            }
+            __syncthreads();
+        }
+        if (!live) continue;                   // no barrier below this line
+        const long px = (long)y * W + x;
+        float* prob = a.prob ? a.prob + px : nullptr;
+        int b1, b2, be;
+        if (ident && C <= SE_SMALL) {
+            const long row = (long)y * W + tx0;                      // the same for all lanes of the wave
+            se_pixel_regs(a.a + row, a.b + row, lane, C, a.prob ? a.prob + row : nullptr, HW, b1, b2, be);
+        } else if (ident) {
+            se_pixel_any<true>(a.a + px, a.b + px, HW, 0, 0, 0, 0, 0.f, 0.f, C, prob, HW, b1, b2, be);
+        } else {
+            int y0, y1, x0, x1;
+            float ly, lx;
+            se_src(y, sy, h, y0, y1, ly);
+            se_src(x, sx, w, x0, x1, lx);
+            if (staged) {
+                const int r0 = (y0 - fy0) * fw - fx0, r1 = (y1 - fy0) * fw - fx0, ps = 2 * Cp;
+                se_pixel_lds(st, Cp, (r0 + x0) * ps, (r0 + x1) * ps, (r1 + x0) * ps, (r1 + x1) * ps, ly, lx, C, prob, HW, b1, b2, be);
+            } else {
+                se_pixel_any<false>(a.a, a.b, hw, y0 * w + x0, y0 * w + x1, y1 * w + x0, y1 * w + x1, ly, lx, C, prob, HW, b1, b2, be);
+            }
+        }
+        if (a.pred) a.pred[px] = be;
+        if (!want_hist && !want_cnt) continue;
+        const long long g = a.gt[px];
+        if (g < 0 || g >= C) continue;         // evaluate._fast_hist: pixels with gt outside [0, C) are skipped
+        ++n_valid;
+        n_agree += b1 == b2 ? 1 : 0;
+        if (!want_hist) continue;
+        const int row = (int)g * C, cc = C * C;
+        const int i1 = row + b1, i2 = cc + row + b2, i3 = 2 * cc + row + be;
+        if (priv) {
+            atomicAdd(&bins32[i1 >> 1], 1u << ((i1 & 1) * 16));
+            atomicAdd(&bins32[i2 >> 1], 1u << ((i2 & 1) * 16));
+            atomicAdd(&bins32[i3 >> 1], 1u << ((i3 & 1) * 16));
+        } else {
+            atomicAdd(&a.hist[i1], 1ull);
+            atomicAdd(&a.hist[i2], 1ull);
+            atomicAdd(&a.hist[i3], 1ull);
+        }
+    }
+    if (priv) {
+        __syncthreads();
+        for (int i = tid; i < nb; i += SE_THREADS) {
+            const unsigned int v = (bins32[i >> 1] >> ((i & 1) * 16)) & 0xffffu;
+            if (v) atomicAdd(&a.hist[i], (unsigned long long)v);
+        }
+    }
+    if (want_cnt) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            n_valid += __shfl_xor(n_valid, o, 64);
+            n_agree += __shfl_xor(n_agree, o, 64);
+        }
+        if ((tid & 63) == 0 && n_valid) {
+            atomicAdd(&a.counts[0], (unsigned long long)n_valid);
+            if (n_agree) atomicAdd(&a.counts[1], (unsigned long long)n_agree);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int dupl_seg_ensemble(const dupl_seg_ensemble_desc* d, dupl_stream_t stream) {
+    if (!d || d->struct_size != sizeof(dupl_seg_ensemble_desc)) return DUPL_ERR_ARG;
+    if (!d->a || !d->b) return DUPL_ERR_ARG;
+    if (d->C < 1 || d->C > DUPL_SEG_ENSEMBLE_MAX_C || d->h <= 0 || d->w <= 0 || d->H <= 0 || d->W <= 0) return DUPL_ERR_ARG;
+    if ((long)d->H * d->W > 0x7ffffff0L || (long)d->h * d->w > 0x7ffffff0L) return DUPL_ERR_ARG;
+    if (!d->hist && !d->counts && !d->pred && !d->prob) return DUPL_ERR_ARG;
+    if ((d->hist || d->counts) && !d->gt) return DUPL_ERR_ARG;
+    SegEnsArgs a;
+    a.a = d->a; a.b = d->b; a.gt = (const long long*)d->gt;
+    a.hist = (unsigned long long*)d->hist; a.counts = (unsigned long long*)d->counts;
+    a.pred = (long long*)d->pred; a.prob = d->prob;
+    a.C = d->C; a.h = d->h; a.w = d->w; a.H = d->H; a.W = d->W;
+    const int nb = 3 * d->C * d->C;
+    a.priv = d->hist && nb <= SE_BINS;
+    a.bin_words = a.priv ? (((nb + 1) / 2 + 3) & ~3) : 0;               // the stage behind it stays 16-byte aligned
+    a.stage_cap = 0;
+    if (d->h != d->H || d->w != d->W) {
+        // an upper bound of a tile's footprint; the kernel checks every tile's own footprint against stage_cap
+        const double sy = (double)d->h / d->H, sx = (double)d->w / d->W;
+        long fh = (long)((SE_TH - 1) * sy) + 4, fw = (long)((SE_TW - 1) * sx) + 4;
+        if (fh > d->h) fh = d->h;
+        if (fw > d->w) fw = d->w;
+        const long need = fh * fw * 2 * ((d->C + 3) & ~3);
+        a.stage_cap = need <= SE_STAGE ? (int)need : 0;
+    }
+    a.tiles_x = (d->W + SE_TW - 1) / SE_TW;
+    const long ntiles = (long)a.tiles_x * ((d->H + SE_TH - 1) / SE_TH);
+    if (ntiles > 0x7fffffffL) return DUPL_ERR_ARG;
+    a.ntiles = (int)ntiles;
+    long grid = ntiles < 2048 ? ntiles : 2048;
+    if (a.priv && grid * SE_BLOCK_TILES < ntiles) grid = (ntiles + SE_BLOCK_TILES - 1) / SE_BLOCK_TILES;
+    const size_t lds = sizeof(unsigned int) * (size_t)a.bin_words + sizeof(float) * (size_t)a.stage_cap;
+    DUPL_LAUNCH(seg_ens_kernel, dim3((unsigned)grid), dim3(SE_THREADS), lds, (hipStream_t)stream, a);
+    return dupl_launch_status();
+}

@@ -1102,3 +1102,43 @@ def cam_overlay(value: Tensor, inputs: Optional[Tensor] = None, alpha: float = 0
     out = torch.empty((B, H, W, 3), device=value.device, dtype=torch.uint8)
     L().dupl_cam_overlay(value.data_ptr(), _p(inputs), out.data_ptr(), B, H, W, float(alpha), None, _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------ ensemble of the two students (csrc/seg_ens.hip)
+def seg_ensemble(a: Tensor, b: Tensor, size, gt: Optional[Tensor] = None, hist: Optional[Tensor] = None,
+                 counts: Optional[Tensor] = None, want_pred: bool = False, want_prob: bool = False):
+    """One pass over the (H,W) = size grid for the two students' accumulated logits a, b ((C,h,w) or (1,C,h,w)): per pixel
+    u_s = the bilinear (align_corners False) up-sampling of student s (the logits themselves when (h,w) == (H,W)),
+    e = (softmax_c(u_1) + softmax_c(u_2)) / 2, and the argmax of u_1, u_2 and e; then
+      hist (3,C,C) int64 += evaluate._fast_hist(gt, prediction) of student 1, student 2, the ensemble (needs gt (H,W) int64),
+      counts (2,) int64 += (pixels with valid gt, those on which the two students agree) (needs gt),
+      pred (H,W) int64 = argmax_c e,   prob (C,H,W) fp32 = e.
+    Returns (pred or None, prob or None); hist and counts are updated in place."""
+    if a.dim() == 4:
+        assert a.shape[0] == 1 and b.shape[0] == 1, "seg_ensemble takes one image per call"
+        a, b = a[0], b[0]
+    assert a.dim() == 3 and a.shape == b.shape, f"a, b: (C,h,w) of equal shape, got {tuple(a.shape)} and {tuple(b.shape)}"
+    C, h, w = a.shape
+    H, W = int(size[0]), int(size[1])
+    if not 1 <= C <= _lib.SEG_ENSEMBLE_MAX_C:
+        raise ValueError(f"seg_ensemble takes 1 .. {_lib.SEG_ENSEMBLE_MAX_C} channels, got {C}")
+    a, b = _chk(a.contiguous()), _chk(b.contiguous())
+    dev = a.device
+    if hist is not None or counts is not None:
+        assert gt is not None, "seg_ensemble: hist and counts need gt"
+        assert gt.is_cuda and gt.dtype == torch.int64 and gt.numel() == H * W, f"gt: (H,W) int64 on the device, got {tuple(gt.shape)}"
+        gt = gt.contiguous()
+    if hist is not None:
+        assert hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and tuple(hist.shape) == (3, C, C), \
+            f"hist must be (3, C, C) int64, got {tuple(hist.shape)}"
+    if counts is not None:
+        assert counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and tuple(counts.shape) == (2,)
+    if hist is None and counts is None and not want_pred and not want_prob:
+        raise ValueError("seg_ensemble: nothing asked for (hist, counts, want_pred, want_prob)")
+    pred = torch.empty((H, W), device=dev, dtype=torch.int64) if want_pred else None
+    prob = torch.empty((C, H, W), device=dev, dtype=torch.float32) if want_prob else None
+    d = _lib.SegEnsembleDesc(C=C, h=h, w=w, H=H, W=W, a=a.data_ptr(), b=b.data_ptr(),
+                             gt=_p(gt) if (hist is not None or counts is not None) else None, hist=_p(hist), counts=_p(counts),
+                             pred=_p(pred), prob=_p(prob))
+    L().dupl_seg_ensemble(ctypes.byref(d), _stream())
+    return pred, prob

@@ -10,7 +10,10 @@ an element-wise max -- fused into one accumulate kernel per scale (csrc/eval.hip
 format (torch.save(model.state_dict()) of the DDP-wrapped model: keys prefixed `module.`, train_final_voc.py:514-519).
 With `--crf 1` the reference's `crf_proc` follows on the device (`crf_proc` below): DenseCRF(10, 1, 1, 4, 121, 5) on the better
 student's saved logits, `seg_crf` scores and the prediction PNGs.  It is the exact mean-field update (utils/dcrf.py of this
-package, csrc/crf.hip), not pydensecrf's lattice approximation, and its scores have not been compared with pydensecrf's."""
+package, csrc/crf.hip), not pydensecrf's lattice approximation, and its scores have not been compared with pydensecrf's.
+Beyond the reference, `--ensemble 1` also scores the mean of the two students' class probabilities: per image one fused pass
+(ops.seg_ensemble, csrc/seg_ens.hip) up-samples both students' logits and fills the three confusion matrices and the students'
+agreement counters; `--crf_branch ens` runs the CRF stage on that mean.  Without these flags nothing changes."""
 from collections import OrderedDict
 
 import torch
@@ -84,66 +87,86 @@ def msc_seg_logits_coco(model, inputs, scales=(1.0, 1.25, 1.5), size=448):
     return accs[0], accs[1]
 
 
-def validate_coco(model, data_loader, args, num_classes=81, cat_list=None, process_group=None, keep_logits=None):
+def _ensemble_scores(em):
+    """[student 1, student 2, ensemble] of an EnsembleMatrix; the ensemble's dict also carries "agree", the share of the valid
+    pixels on which the two students predict the same class."""
+    sc = em.scores()
+    sc[2]["agree"] = em.agreement()
+    return sc
+
+
+def validate_coco(model, data_loader, args, num_classes=81, cat_list=None, process_group=None, keep_logits=None, ensemble=False):
     """eval_seg_coco_ddp._validate on this rank's shard of the loader (the reference splits the val set round-robin over
     the ranks, tools/eval_seg_coco_ddp.py:239-245, and every rank scores its own shard).  With `process_group` (or an
     initialised default group) the per-rank confusion matrices are additionally summed over the ranks -- nc^2 int64
-    counters, the only exchange of the evaluation path -- so that every rank returns the scores of the WHOLE set."""
+    counters, the only exchange of the evaluation path -- so that every rank returns the scores of the WHOLE set.
+    ensemble=True: one fused pass per image (ops.seg_ensemble) up-samples both students' logits, scores each student and the mean
+    of their class probabilities -> (seg_score_1, seg_score_2, seg_score_ens); the students' scores are the same counts."""
     import torch.distributed as dist
     from ..utils.train_helper import _device_of, _fetch
     dev = _device_of(model)
     cms = [evaluate.ConfusionMatrix(num_classes, dev) for _ in range(2)]
+    em = evaluate.EnsembleMatrix(num_classes, dev) if ensemble else None
     model.eval()
     scales = getattr(args, "scales", (1.0, 1.25, 1.5))
     for data in data_loader:
         inputs, labels, _ = _fetch(data, dev)
         seg = msc_seg_logits_coco(model, inputs, scales, getattr(args, "crop_size", 448))
         H, W = labels.shape[1:]
+        if ensemble:
+            em.update(seg[0], seg[1], labels)
         for k in range(2):
-            cms[k].update(labels, ops.upsample_argmax(seg[k], H, W))
+            if not ensemble:
+                cms[k].update(labels, ops.upsample_argmax(seg[k], H, W))
             if keep_logits is not None:          # eval_seg_coco_ddp.py:127-128 saves the summed low-resolution logits
                 keep_logits(data[0], k + 1, seg[k])
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
-        for c in cms:
-            dist.all_reduce(c.hist, op=dist.ReduceOp.SUM, group=process_group)
-    sc = [c.scores() for c in cms]
+        for t in ([em.hist, em.counts] if ensemble else [c.hist for c in cms]):
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
+    sc = _ensemble_scores(em) if ensemble else [c.scores() for c in cms]
     if cat_list is not None:
-        print(format_tabs(sc, ["Seg_1", "Seg_2"], cat_list=cat_list))
-    return sc[0], sc[1]
+        print(format_tabs(sc, ["Seg_1", "Seg_2", "Seg_ens"][:len(sc)], cat_list=cat_list))
+    return tuple(sc)
 
 
-def validate(model, data_loader, args, num_classes=21, cat_list=None, keep_logits=None):
+def validate(model, data_loader, args, num_classes=21, cat_list=None, keep_logits=None, ensemble=False):
     """eval_seg_voc._validate: multi-scale seg predictions of both students over a loader of
     (name, inputs (1,3,h,w), labels (1,H,W), cls_label) -> (seg_score_1, seg_score_2).
     keep_logits(name, branch, logits) is called with the (1,C1,H,W) device logits (the reference np.save()s them for the
-    CRF stage)."""
+    CRF stage).  ensemble=True: one fused pass per image (ops.seg_ensemble) scores each student and the mean of their class
+    probabilities -> (seg_score_1, seg_score_2, seg_score_ens); the students' scores are the same counts."""
     from ..utils.train_helper import _device_of, _fetch
     dev = _device_of(model)
     cms = [evaluate.ConfusionMatrix(num_classes, dev) for _ in range(2)]
+    em = evaluate.EnsembleMatrix(num_classes, dev) if ensemble else None
     model.eval()
     for data in data_loader:
         inputs, labels, _ = _fetch(data, dev)
         seg = msc_seg_logits(model, inputs, labels.shape[1:], getattr(args, "scales", (1.0, 1.5, 1.25)))
+        if ensemble:
+            em.update(seg[0], seg[1], labels)
         for k in range(2):
-            cms[k].update(labels, ops.argmax_channels(seg[k]))
+            if not ensemble:
+                cms[k].update(labels, ops.argmax_channels(seg[k]))
             if keep_logits is not None:
                 keep_logits(data[0], k + 1, seg[k])
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         # main() shards the split over the ranks for both datasets: the score is of the summed confusion matrices
-        for c in cms:
-            dist.all_reduce(c.hist, op=dist.ReduceOp.SUM)
-    sc = [c.scores() for c in cms]
+        for t in ([em.hist, em.counts] if ensemble else [c.hist for c in cms]):
+            dist.all_reduce(t, op=dist.ReduceOp.SUM)
+    sc = _ensemble_scores(em) if ensemble else [c.scores() for c in cms]
     if cat_list is not None and (not dist.is_initialized() or dist.get_rank() == 0):
-        print(format_tabs(sc, ["Seg_1", "Seg_2"], cat_list=cat_list))
-    return sc[0], sc[1]
+        print(format_tabs(sc, ["Seg_1", "Seg_2", "Seg_ens"][:len(sc)], cat_list=cat_list))
+    return tuple(sc)
 
 
 def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb_dir, num_classes, dev, process_group=None):
     """tools/eval_seg_voc.py:94-153 / tools/eval_seg_coco_ddp.py:142-202 on the device, over this rank's `names`: per image the
     saved logits of `branch` are resized to the JPEG's size, softmax + DenseCRF(10, 1, 1, 4, 121, 5) + argmax run on the device,
     the label PNG (and the palette PNG) are written and a device ConfusionMatrix is accumulated; with several ranks the
-    matrices are summed.  image_path(name) -> JPEG path; label_of(name, image) -> (H,W) ground truth.  Returns the scores."""
+    matrices are summed.  image_path(name) -> JPEG path; label_of(name, image) -> (H,W) ground truth.  Returns the scores.
+    branch "ens": both students' saved logits go through ops.seg_ensemble and the CRF runs on the mean of their probabilities."""
     import os
     import numpy as np
     import torch.distributed as dist
@@ -155,13 +178,20 @@ def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb
     for d in (segs_dir, segs_rgb_dir):
         if d:
             os.makedirs(d, exist_ok=True)
+    def saved(b, name):
+        z = np.load(os.path.join(logits_dir, b, name + ".npy"), allow_pickle=True).item()["msc_seg"]
+        return torch.from_numpy(np.ascontiguousarray(z, dtype=np.float32)).to(dev)
+
     for name in names:
-        logit = np.load(os.path.join(logits_dir, branch, name + ".npy"), allow_pickle=True).item()["msc_seg"]
         with Image.open(image_path(name)) as im:
             image = np.ascontiguousarray(np.array(im.convert("RGB")), dtype=np.uint8)
         H, W, _ = image.shape
-        logit = ops.resize_bilinear(torch.from_numpy(np.ascontiguousarray(logit, dtype=np.float32)).to(dev), H, W)
-        Q = post.from_logits(torch.from_numpy(image).to(dev), logit[0])
+        if branch == "ens":       # the mean of the two students' class probabilities at the JPEG's size, one fused pass
+            _, prob = ops.seg_ensemble(saved("branch1", name), saved("branch2", name), (H, W), want_prob=True)
+            Q = post(torch.from_numpy(image).to(dev), prob)
+        else:
+            logit = ops.resize_bilinear(saved(branch, name), H, W)
+            Q = post.from_logits(torch.from_numpy(image).to(dev), logit[0])
         pred = ops.argmax_channels(Q[None])[0]
         label = torch.from_numpy(np.ascontiguousarray(label_of(name, image)).astype(np.int64)).to(dev)
         cm.update(label, pred)
@@ -205,11 +235,45 @@ def build_parser(dataset: str = "voc"):
                    help="1: run the reference's crf_proc on the device after the inference (DenseCRF(10, 1, 1, 4, 121, 5) on the "
                         "better student's saved logits; needs --save_logits 1): prints the seg_crf table, writes "
                         "<run>/segs/seg_preds/<infer_set>/<name>.png (+ the palette PNGs)")
+    p.add_argument("--ensemble", default=0, type=int, choices=(0, 1),
+                   help="1: also score the mean of the two students' class probabilities (one fused pass per image, ops.seg_ensemble): "
+                        "a third table column Seg_ens, 'Seg_ens mIoU' and the students' agreement 'agree' in the last line")
+    p.add_argument("--crf_branch", default="auto", choices=("auto", "1", "2", "ens"),
+                   help="what --crf 1 post-processes: auto = the highest mIoU (of the two students, or with --ensemble 1 of the "
+                        "students and the ensemble; on equal mIoU the students' rule, then the ensemble last), 1 / 2 = that "
+                        "student, ens = the ensemble (needs --ensemble 1)")
     p.add_argument("--nograd_gemm", default=os.environ.get("DUPL_NOGRAD_GEMM", "f16x3"), choices=("f16x3", "f16"),
                    help="GEMMs and attention of the no-grad encoder passes (multi-scale CAM, validation, inference): f16x3 = three f16 products, "
                         "fp32-equivalent (default); f16 = one product on the hi planes, fp32 accumulation (engine.set_nograd_gemm_mode; "
                         "experimental)")
     return p
+
+
+ENS_NEEDS_FLAG = "--crf_branch ens post-processes the ensemble of the two students: it requires --ensemble 1"
+
+
+def check_branch_args(args):
+    """Refuse flag combinations that cannot be served, before anything is loaded."""
+    if args.crf_branch == "ens" and not args.ensemble:
+        raise SystemExit(ENS_NEEDS_FLAG)
+
+
+def pick_crf_branch(choice, s1, s2, ens=None):
+    """The logits crf_proc runs on: "branch1", "branch2" or "ens".  auto without an ensemble score is the reference's rule
+    (eval_seg_voc.py:185-188: student 1 only when strictly better); auto with one takes the highest mIoU of the three, and on
+    equal mIoU the earliest of branch1, branch2, ens."""
+    if choice in ("1", "2"):
+        return "branch" + choice
+    if choice == "ens":
+        return "ens"
+    if ens is None:
+        return "branch1" if s1["miou"] > s2["miou"] else "branch2"
+    cand = [("branch1", s1["miou"]), ("branch2", s2["miou"]), ("ens", ens["miou"])]
+    best = cand[0]
+    for c in cand[1:]:
+        if c[1] > best[1]:
+            best = c
+    return best[0]
 
 
 def main(argv=None):
@@ -229,6 +293,7 @@ def main(argv=None):
     pre.add_argument("--dataset", default="voc", choices=("voc", "coco"))
     is_voc = pre.parse_known_args(argv)[0].dataset == "voc"
     args = build_parser("voc" if is_voc else "coco").parse_args(argv)
+    check_branch_args(args)
     from .. import engine
     engine.set_nograd_gemm_mode(args.nograd_gemm)
     if isinstance(args.scales, str):
@@ -270,17 +335,23 @@ def main(argv=None):
 
     with torch.no_grad():
         if is_voc:
-            s1, s2 = validate(model, loader, args, args.num_classes, voc.class_list, keep_logits=keep)
+            sc = validate(model, loader, args, args.num_classes, voc.class_list, keep_logits=keep, ensemble=bool(args.ensemble))
         else:
-            s1, s2 = validate_coco(model, loader, args, args.num_classes, coco.class_list, keep_logits=keep)
+            sc = validate_coco(model, loader, args, args.num_classes, coco.class_list, keep_logits=keep, ensemble=bool(args.ensemble))
+    s1, s2 = sc[0], sc[1]
+    ens = sc[2] if args.ensemble else None
+    last = {"Seg_1 mIoU": s1["miou"], "Seg_2 mIoU": s2["miou"]}
+    if ens is not None:
+        last.update({"Seg_ens mIoU": ens["miou"], "agree": ens["agree"]})
+    # crf_proc (eval_seg_voc.py:185-188): the student with the higher mIoU unless --crf_branch / --ensemble say otherwise
+    branch = pick_crf_branch(args.crf_branch, s1, s2, ens)
     rank0 = int(os.environ.get("RANK", "0")) == 0
     if not args.crf:
         if rank0:
-            print({"Seg_1 mIoU": s1["miou"], "Seg_2 mIoU": s2["miou"],
-                   "next": f"DenseCRF over {logits_dir}/branch{1 if s1['miou'] > s2['miou'] else 2} (reference: crf_proc, CPU)"})
-        return s1, s2
-    # crf_proc (eval_seg_voc.py:185-188): the student with the higher mIoU; images sharded like the logits pass
-    branch = "branch1" if s1["miou"] > s2["miou"] else "branch2"
+            over = "both students' logits under " + logits_dir if branch == "ens" else f"{logits_dir}/{branch}"
+            print({**last, "next": f"DenseCRF over {over} (reference: crf_proc, CPU)"})
+        return tuple(sc)
+    # images sharded like the logits pass
     base = ds.dataset if world > 1 else ds
     names = [str(n) for n in base.name_list][(dist.get_rank() if world > 1 else 0)::world]
     test_set = "test" in args.infer_set
@@ -305,8 +376,8 @@ def main(argv=None):
                        rgb_dir, args.num_classes, dev)
     if rank0:
         print(format_tabs([crf], ["seg_crf"], cat_list=voc.class_list if is_voc else coco.class_list))
-        print({"Seg_1 mIoU": s1["miou"], "Seg_2 mIoU": s2["miou"], "seg_crf mIoU": crf["miou"]})
-    return s1, s2, crf
+        print({**last, "seg_crf mIoU": crf["miou"]})
+    return tuple(sc) + (crf,)
 
 
 if __name__ == "__main__":

@@ -71,6 +71,30 @@ class ConfusionMatrix:
         return scores_from_hist(self.hist.cpu().numpy())
 
 
+class EnsembleMatrix:
+    """Device-resident (3, nc, nc) int64 histograms -- student 1, student 2, the mean of their class probabilities -- and the
+    (2,) int64 counters (pixels with valid gt, pixels on which the two students agree), filled image by image by the fused pass
+    ops.seg_ensemble (csrc/seg_ens.hip): rows 0 and 1 are what two ConfusionMatrix.update calls on the students' own predictions give."""
+
+    def __init__(self, num_classes, device):
+        self.num_classes = int(num_classes)
+        self.hist = torch.zeros((3, self.num_classes, self.num_classes), device=device, dtype=torch.int64)
+        self.counts = torch.zeros((2,), device=device, dtype=torch.int64)
+
+    def update(self, a, b, gt):
+        """a, b: the students' accumulated logits (1,C,h,w) or (C,h,w); gt (1,H,W) or (H,W) int64; the logits are up-sampled to gt's size."""
+        ops.seg_ensemble(a, b, gt.shape[-2:], gt=gt.reshape(gt.shape[-2:]), hist=self.hist, counts=self.counts)
+
+    def scores(self):
+        """[student 1, student 2, ensemble] score dicts."""
+        return [scores_from_hist(h) for h in self.hist.cpu().numpy()]
+
+    def agreement(self):
+        """The share of the valid pixels on which the two students predict the same class (nan before any valid pixel)."""
+        n, same = (int(v) for v in self.counts.cpu())
+        return same / n if n else float("nan")
+
+
 class ThresholdSweep:
     """Device-resident (T, nc, nc) int64 histograms, one confusion matrix per background threshold, filled by the fused pass
     ops.cam_eval (csrc/cam_eval.hip): T thresholds cost the same pass over the label grid as one."""

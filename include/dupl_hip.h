@@ -667,6 +667,29 @@ int dupl_cam_eval(const dupl_cam_eval_desc* d, dupl_stream_t stream);
 int dupl_cam_overlay(const float* value, const float* img, uint8_t* out, int32_t B, int32_t H, int32_t W, double alpha,
                      const float* mean_std, dupl_stream_t s);
 
+/* ------------------------------------------------------------------ ensemble of the two students (csrc/seg_ens.hip)
+ * The evaluation tail of tools/eval_seg --ensemble 1 in one pass over the (H,W) label grid.  Per output pixel:
+ *   u_s[c] = bilinear (align_corners False) up-sampling of student s's logits to (H,W) -- the arithmetic of dupl_upsample_argmax;
+ *            with (h,w) == (H,W) the logits themselves, nothing is interpolated;
+ *   p_s = softmax_c(u_s) (channel maximum subtracted);   e = (p_1 + p_2) / 2;
+ *   predictions = argmax_c of u_1, u_2 and e (first maximum wins, as dupl_argmax_channels).
+ * u_s and p_s are never written to memory.  Every output is optional, at least one is required.  hist and counts are ADDED to,
+ * with integer atomics only: bit-reproducible. */
+#define DUPL_SEG_ENSEMBLE_MAX_C 255
+typedef struct dupl_seg_ensemble_desc {
+    uint32_t struct_size;        /* sizeof(dupl_seg_ensemble_desc), checked */
+    int32_t C, h, w;             /* a, b: (C,h,w) fp32; 1 <= C <= DUPL_SEG_ENSEMBLE_MAX_C */
+    int32_t H, W;                /* output grid */
+    const float* a;              /* student 1's accumulated logits */
+    const float* b;              /* student 2's */
+    const int64_t* gt;           /* (H,W) ground truth; required with hist or counts; values outside [0, C) are skipped */
+    int64_t* hist;               /* (3,C,C), hist[r][gt][pred] += counts; r = 0 student 1, 1 student 2, 2 the ensemble; or NULL */
+    int64_t* counts;             /* [2]: [0] += pixels with valid gt, [1] += those on which the two students agree; or NULL */
+    int64_t* pred;               /* (H,W) the ensemble's prediction; or NULL */
+    float* prob;                 /* (C,H,W) the ensemble's probabilities e; or NULL */
+} dupl_seg_ensemble_desc;
+int dupl_seg_ensemble(const dupl_seg_ensemble_desc* d, dupl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,9 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] | backbone | nograd
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd
 `crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81.
 `cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces.
+`seg_ensemble` (only when named) times the fused ensemble tail of tools/eval_seg --ensemble 1 (ops.seg_ensemble) against the composition
+of existing ops that yields the same matrices, at the VOC and the COCO form.
 `backbone` (only when named; then nothing else runs) times one phase-B training step at VOC 448^2, 4 images, two student streams
 for every registered --backbone, or for the names that follow it: bench.py's own workload and timed region (bench.Workload.measure:
 warm-up steps, then K steps between synchronisations), so the deit_base_patch16_224 row is bench.py's figure.
@@ -102,6 +104,62 @@ def cam_eval_bench(dev, g):
                   f"composed {t_c:.1f} us ({t_c / t_f:.1f}x ops.cam_eval); with the global-atomics histogram {t_g:.1f} us")
 
 
+def seg_ensemble_bench(dev, g):
+    """ops.seg_ensemble (three confusion matrices + the agreement counters, one launch; with and without the (C,H,W) probabilities)
+    against the composition of existing ops that yields the same matrices and counters: resize_bilinear x 2 -> softmax x 2 -> mean ->
+    argmax_channels x 3 -> confusion_accum x 3 (+ the two masked sums of the counters), per call at batch 1.  VOC form: 375 x 500,
+    C = 21, logits at label size (smooth, as accumulated from up-sampled maps); COCO form: 480 x 640, C = 81, logits 28 x 28.  Floor bytes of the fused pass: both students' logits
+    once + 8 B/px of gt (+ 4 C B/px of prob); the rate printed is those bytes over the time of the call, wrapper included."""
+    from dupl_amd.utils import evaluate
+    for name, C, h, w, H, W in (("VOC", 21, 375, 500, 375, 500), ("COCO", 81, 28, 28, 480, 640)):
+        # logits as a network gives them: smooth at label size (the VOC form accumulates up-sampled 1/16-resolution maps), so that
+        # predictions come in regions and a workgroup's pixels fall into a few histogram bins; i.i.d. noise per pixel would make
+        # every workgroup flush hundreds of counters and time the atomics instead
+        def logits():
+            if h <= 32:
+                return (torch.randn((1, C, h, w), generator=g) * 3).to(dev)
+            up = torch.nn.functional.interpolate(torch.randn((1, C, 24, 32), generator=g) * 3, size=(h, w), mode="bilinear", align_corners=False)
+            return (up + 0.05 * torch.randn((1, C, h, w), generator=g)).contiguous().to(dev)
+
+        a, b = logits(), logits()
+        gt = torch.randint(0, C, (1, 1, 6, 8), generator=g).float()
+        gt[0, 0, 0, :2] = 255.0
+        gt = torch.nn.functional.interpolate(gt, size=(H, W), mode="nearest")[0, 0].long().to(dev)
+        em = evaluate.EnsembleMatrix(C, dev)
+        cms = [evaluate.ConfusionMatrix(C, dev) for _ in range(3)]
+        cnt = torch.zeros(2, device=dev, dtype=torch.int64)
+
+        def composed():
+            ua, ub = ops.resize_bilinear(a, H, W), ops.resize_bilinear(b, H, W)
+            e = (torch.softmax(ua, 1) + torch.softmax(ub, 1)) * 0.5
+            pa, pb, pe = ops.argmax_channels(ua)[0], ops.argmax_channels(ub)[0], ops.argmax_channels(e)[0]
+            for cm, p in zip(cms, (pa, pb, pe)):
+                cm.update(gt, p)
+            ok = (gt >= 0) & (gt < C)
+            cnt[0] += ok.sum()
+            cnt[1] += (ok & (pa == pb)).sum()
+            return e
+
+        def composed_hist_only():        # without the counters' two masked sums (five more launches the fused pass has no use for)
+            ua, ub = ops.resize_bilinear(a, H, W), ops.resize_bilinear(b, H, W)
+            e = (torch.softmax(ua, 1) + torch.softmax(ub, 1)) * 0.5
+            for cm, p in zip(cms, (ua, ub, e)):
+                cm.update(gt, ops.argmax_channels(p)[0])
+
+        fused = lambda: ops.seg_ensemble(a, b, (H, W), gt=gt, hist=em.hist, counts=em.counts)
+        fused_prob = lambda: ops.seg_ensemble(a, b, (H, W), gt=gt, hist=em.hist, counts=em.counts, want_prob=True)
+        # alternate the two sides twice: the spread between the two rounds is the noise of one lease
+        rounds = [(timeit(fused, n=200), timeit(fused_prob, n=200), timeit(composed, n=50, warm=5), timeit(composed_hist_only, n=50, warm=5))
+                  for _ in range(2)]
+        floor = 2 * C * h * w * 4 + H * W * 8
+        floor_p = floor + C * H * W * 4
+        for i, (t_f, t_p, t_c, t_h) in enumerate(rounds):
+            print(f"seg_ensemble {name} {H}x{W} C={C} from {h}x{w}, round {i}: fused {t_f:.1f} us ({floor / t_f / 1e6:.3f} TB/s of its "
+                  f"{floor / 1e6:.1f} MB floor), fused + prob {t_p:.1f} us ({floor_p / t_p / 1e6:.3f} TB/s of {floor_p / 1e6:.1f} MB); composed "
+                  f"{t_c:.1f} us ({t_c / t_f:.1f}x fused, {t_c / t_p:.1f}x fused + prob), composed without the counters {t_h:.1f} us "
+                  f"({t_h / t_f:.1f}x fused)")
+
+
 def backbone_bench(argv):
     """ms / step and img / s of one phase-B step (VOC, 448^2, 4 images on one GPU, two streams) per backbone."""
     import os
@@ -182,6 +240,11 @@ def main():
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
+    if "seg_ensemble" in which:
+        seg_ensemble_bench(dev, g)
+        which = which - {"seg_ensemble"}
+        if not which:
+            return
     if "cam_eval" in which:
         cam_eval_bench(dev, g)
         if which <= {"cam_eval", "crf"} and "crf" not in which:

@@ -120,6 +120,61 @@ class SegEnsembleDesc(ctypes.Structure):
         self.struct_size = ctypes.sizeof(SegEnsembleDesc)
 
 
+class SegDecideDesc(ctypes.Structure):
+    """Mirror of `dupl_seg_decide_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("C", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+        ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("is_prob", ctypes.c_int32), ("ignore_index", ctypes.c_int32),
+        ("min_conf", ctypes.c_float), ("reserved0", ctypes.c_int32),
+        ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("conf", ctypes.c_void_p), ("label", ctypes.c_void_p),
+        ("stats", ctypes.c_void_p),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(SegDecideDesc)
+
+
+class SegPaintDesc(ctypes.Structure):
+    """Mirror of `dupl_seg_paint_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("alpha256", ctypes.c_int32),
+        ("tint_background", ctypes.c_int32), ("contour", ctypes.c_int32),
+        ("contour_rgb", ctypes.c_uint8 * 3), ("reserved0", ctypes.c_uint8),
+        ("label", ctypes.c_void_p), ("image", ctypes.c_void_p), ("palette", ctypes.c_void_p), ("out", ctypes.c_void_p),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(SegPaintDesc)
+
+
+class WindowGatherDesc(ctypes.Structure):
+    """Mirror of `dupl_window_gather_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("h", ctypes.c_int32), ("w", ctypes.c_int32), ("Hs", ctypes.c_int32),
+        ("Ws", ctypes.c_int32), ("nW", ctypes.c_int32), ("wh", ctypes.c_int32), ("ww", ctypes.c_int32),
+        ("x", ctypes.c_void_p), ("origins", ctypes.c_void_p), ("out", ctypes.c_void_p),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(WindowGatherDesc)
+
+
+class WindowMergeDesc(ctypes.Structure):
+    """Mirror of `dupl_window_merge_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("C", ctypes.c_int32), ("hs", ctypes.c_int32), ("ws", ctypes.c_int32),
+        ("nW", ctypes.c_int32), ("wth", ctypes.c_int32), ("wtw", ctypes.c_int32),
+        ("logits", ctypes.c_void_p), ("origins", ctypes.c_void_p), ("canvas", ctypes.c_void_p),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(WindowMergeDesc)
+
+
 GEMM_A_MCONTIG, GEMM_B_NCONTIG, GEMM_GELU, GEMM_ACCUM = 1, 2, 4, 8
 GEMM_MUL_DGELU, GEMM_RELU, GEMM_MUL_RELUMASK, GEMM_ABS, GEMM_STORE_PRE = 16, 32, 64, 128, 256
 GEMM_C_FRESH = 512            # DUPL_GEMM_C_FRESH (dupl_gemm_f16x3_group)
@@ -142,6 +197,8 @@ SPLIT_MULTI_MAX = 16
 GEMM16_GROUP_MAX = 8          # DUPL_GEMM16_GROUP_MAX
 CAM_EVAL_MAX_T, CAM_EVAL_MAX_C = 64, 255      # DUPL_CAM_EVAL_MAX_T, DUPL_CAM_EVAL_MAX_C
 SEG_ENSEMBLE_MAX_C = 255      # DUPL_SEG_ENSEMBLE_MAX_C
+SEG_DECIDE_MAX_C = 255        # DUPL_SEG_DECIDE_MAX_C
+WINDOW_MAX = 256              # DUPL_WINDOW_MAX
 
 _PROTO = re.compile(r"^\s*int\s+(dupl_\w+)\s*\(([^;{]*)\)\s*;", re.M | re.S)
 
@@ -162,6 +219,14 @@ def _ctype(decl: str):
         return ctypes.POINTER(CamEvalDesc)
     if "dupl_seg_ensemble_desc" in d:
         return ctypes.POINTER(SegEnsembleDesc)
+    if "dupl_seg_decide_desc" in d:
+        return ctypes.POINTER(SegDecideDesc)
+    if "dupl_seg_paint_desc" in d:
+        return ctypes.POINTER(SegPaintDesc)
+    if "dupl_window_gather_desc" in d:
+        return ctypes.POINTER(WindowGatherDesc)
+    if "dupl_window_merge_desc" in d:
+        return ctypes.POINTER(WindowMergeDesc)
     if "*" in d or d.startswith("dupl_stream_t"):
         return ctypes.c_void_p
     base = d.replace("const", "").split()

@@ -12,6 +12,8 @@
 //     through L1, channel by channel.
 // Histograms: 3 C^2 counters of 16 bits privatised per workgroup in LDS where they fit 40 KB (C <= 82) and flushed with 64-bit atomics,
 // otherwise 64-bit atomics straight to hist.  Integer atomics only: the result is bit-reproducible in either mode.
+// seg_decide_kernel (below) is the same pass without a ground truth, for tools/predict: winner, confidence, rejection, label bytes and
+// per-label statistics on the same tiles, for one student, two, or probabilities (DenseCRF's marginals).
 #include "common.h"
 #include "../../include/dupl_hip.h"
 
@@ -68,7 +70,7 @@ constexpr int SE_SMALL = 24;             // identity: channels a thread keeps in
 // scalar base and the lane as offset, so SE_SMALL of them per student are in flight without an address register each).  Both
 // students' values are read ONCE and stay in registers through maximum, partition sum and mean: one exp per value.
 __device__ __forceinline__ void se_pixel_regs(const float* __restrict__ r1, const float* __restrict__ r2, int lane, int C,
-                                              float* __restrict__ prow, long HW, int& b1, int& b2, int& be) {
+                                              float* __restrict__ prow, long HW, int& b1, int& b2, int& be, float& me) {
     float u1[SE_SMALL], u2[SE_SMALL];
 #pragma unroll
     for (int j = 0; j < SE_SMALL; ++j) {       // channels past C read as -inf: exp gives 0 and no argmax takes them
@@ -91,7 +93,7 @@ __device__ __forceinline__ void se_pixel_regs(const float* __restrict__ r1, cons
         s2 += (double)u2[j];
     }
     const float h1 = 0.5f / (float)s1, h2 = 0.5f / (float)s2;          // e = (p1 + p2) / 2 = ex1 * (0.5 / s1) + ex2 * (0.5 / s2)
-    float me = -INFINITY;
+    me = -INFINITY;
     be = 0;
 #pragma unroll
     for (int j = 0; j < SE_SMALL; ++j) {
@@ -114,7 +116,7 @@ __device__ __forceinline__ void se_chunk(const float* st, int t00, int t01, int 
     for (int k = 0; k < 4; ++k) u[k] = c0 + k < C ? se_tap(A[k], B[k], Cc[k], D[k], ly, lx) : -INFINITY;
 }
 __device__ __forceinline__ void se_pixel_lds(const float* st, int Cp, int t00, int t01, int t10, int t11, float ly, float lx, int C,
-                                             float* prob, long HW, int& b1, int& b2, int& be) {
+                                             float* prob, long HW, int& b1, int& b2, int& be, float& me) {
     float m1 = -INFINITY, m2 = -INFINITY;
     double s1 = 0.0, s2 = 0.0;
     b1 = 0; b2 = 0;
@@ -139,7 +141,7 @@ __device__ __forceinline__ void se_pixel_lds(const float* st, int Cp, int t00, i
         s2 = s2 * (double)se_exp(o2 - m2) + (double)a2;
     }
     const float h1 = 0.5f / (float)s1, h2 = 0.5f / (float)s2;
-    float me = -INFINITY;
+    me = -INFINITY;
     be = 0;
 #pragma unroll 2
     for (int c0 = 0; c0 < C; c0 += 4) {
@@ -160,7 +162,7 @@ __device__ __forceinline__ void se_pixel_lds(const float* st, int Cp, int t00, i
 // plane stride and o00 .. o11 the four taps inside a plane.
 template <bool IDENT>
 __device__ __forceinline__ void se_pixel_any(const float* q1, const float* q2, long ps, int o00, int o01, int o10, int o11, float ly,
-                                             float lx, int C, float* prob, long HW, int& b1, int& b2, int& be) {
+                                             float lx, int C, float* prob, long HW, int& b1, int& b2, int& be, float& me) {
     auto val = [&](const float* q, int c) -> float {
         const float* p = q + (long)c * ps;
         if (IDENT) return p[0];
@@ -179,13 +181,58 @@ __device__ __forceinline__ void se_pixel_any(const float* q1, const float* q2, l
         s2 += (double)se_exp(val(q2, c) - m2);
     }
     const float h1 = 0.5f / (float)s1, h2 = 0.5f / (float)s2;
-    float me = -INFINITY;
+    me = -INFINITY;
     be = 0;
     for (int c = 0; c < C; ++c) {
         const float e = fmaf(se_exp(val(q1, c) - m1), h1, se_exp(val(q2, c) - m2) * h2);
         if (e > me) { me = e; be = c; }
         if (prob) prob[(long)c * HW] = e;
     }
+}
+
+// Stage the source pixels under the output tile at (ty0, tx0), both students, where they fit stage_cap floats (every thread of the
+// workgroup calls this: two barriers).  The source index is monotone in the output coordinate, so the first row's y0 and the last
+// row's y1 bound every tap of the tile (the same for the columns).  Returns whether the tile is staged; fy0, fx0, fw: the footprint.
+__device__ __forceinline__ bool se_stage_tile(const float* __restrict__ pa, const float* __restrict__ pb, float* st, int tid, int ty0,
+                                              int tx0, int C, int h, int w, int H, int W, float sy, float sx, int stage_cap, int& fy0,
+                                              int& fx0, int& fw) {
+    const int Cp = (C + 3) & ~3;
+    const long hw = (long)h * w;
+    int i1, j0;
+    float l;
+    const int ty1 = ty0 + SE_TH - 1 < H ? ty0 + SE_TH - 1 : H - 1, tx1 = tx0 + SE_TW - 1 < W ? tx0 + SE_TW - 1 : W - 1;
+    se_src(ty0, sy, h, fy0, i1, l);
+    se_src(ty1, sy, h, j0, i1, l);
+    const int fh = i1 - fy0 + 1;
+    se_src(tx0, sx, w, fx0, i1, l);
+    se_src(tx1, sx, w, j0, i1, l);
+    fw = i1 - fx0 + 1;
+    const bool staged = (long)fh * fw * 2 * Cp <= (long)stage_cap;
+    __syncthreads();                           // the previous tile's taps are read
+    if (staged) {
+        // read in source order (consecutive threads on consecutive columns), written channel-fastest
+        const int plane = fh * fw, n = 2 * Cp * plane;
+        for (int i = tid; i < n; i += SE_THREADS) {
+            const int pc = i / plane, rq = i - pc * plane, r = rq / fw, q = rq - r * fw;
+            const int sidx = pc >= Cp ? 1 : 0, c = pc - sidx * Cp;
+            const float* src = (sidx ? pb : pa) + (long)c * hw;
+            st[(rq * 2 + sidx) * Cp + c] = c < C ? src[(long)(fy0 + r) * w + fx0 + q] : 0.f;
+        }
+    }
+    __syncthreads();
+    return staged;
+}
+
+// the floats of stage a launch asks for: an upper bound of a tile's footprint (the kernels check every tile's own footprint against
+// it), 0 where that does not fit SE_STAGE or nothing is interpolated
+inline int se_stage_floats(int C, int h, int w, int H, int W) {
+    if (h == H && w == W) return 0;
+    const double sy = (double)h / H, sx = (double)w / W;
+    long fh = (long)((SE_TH - 1) * sy) + 4, fw = (long)((SE_TW - 1) * sx) + 4;
+    if (fh > h) fh = h;
+    if (fw > w) fw = w;
+    const long need = fh * fw * 2 * ((C + 3) & ~3);
+    return need <= SE_STAGE ? (int)need : 0;
 }
 
 __global__ __launch_bounds__(SE_THREADS) void seg_ens_kernel(const SegEnsArgs a) {
@@ -209,43 +256,19 @@ __global__ __launch_bounds__(SE_THREADS) void seg_ens_kernel(const SegEnsArgs a)
         const int ty0 = (t / a.tiles_x) * SE_TH, tx0 = (t % a.tiles_x) * SE_TW;
         const int x = tx0 + lane, y = ty0 + wrow;
         const bool live = x < W && y < H;
-        int fy0 = 0, fx0 = 0, fh = 0, fw = 0;
+        int fy0 = 0, fx0 = 0, fw = 0;
         bool staged = false;
-        if (!ident) {
-            // the source pixels under this tile: the index is monotone in the output coordinate, so the first row's y0 and the last
-            // row's y1 bound every tap of the tile (the same for the columns); the same for every thread of the workgroup
-            int i1, j0;
-            float l;
-            const int ty1 = ty0 + SE_TH - 1 < H ? ty0 + SE_TH - 1 : H - 1, tx1 = tx0 + SE_TW - 1 < W ? tx0 + SE_TW - 1 : W - 1;
-            se_src(ty0, sy, h, fy0, i1, l);
-            se_src(ty1, sy, h, j0, i1, l);
-            fh = i1 - fy0 + 1;
-            se_src(tx0, sx, w, fx0, i1, l);
-            se_src(tx1, sx, w, j0, i1, l);
-            fw = i1 - fx0 + 1;
-            staged = (long)fh * fw * 2 * Cp <= (long)a.stage_cap;
-            __syncthreads();                   // the previous tile's taps are read
-            if (staged) {
-                // read in source order (consecutive threads on consecutive columns), written channel-fastest
-                const int plane = fh * fw, n = 2 * Cp * plane;
-                for (int i = tid; i < n; i += SE_THREADS) {
-                    const int pc = i / plane, rq = i - pc * plane, r = rq / fw, q = rq - r * fw;
-                    const int sidx = pc >= Cp ? 1 : 0, c = pc - sidx * Cp;
-                    const float* src = (sidx ? a.b : a.a) + (long)c * hw;
-                    st[(rq * 2 + sidx) * Cp + c] = c < C ? src[(long)(fy0 + r) * w + fx0 + q] : 0.f;
-                }
-            }
-            __syncthreads();
-        }
+        if (!ident) staged = se_stage_tile(a.a, a.b, st, tid, ty0, tx0, C, h, w, H, W, sy, sx, a.stage_cap, fy0, fx0, fw);
         if (!live) continue;                   // no barrier below this line
         const long px = (long)y * W + x;
         float* prob = a.prob ? a.prob + px : nullptr;
         int b1, b2, be;
+        float me;
         if (ident && C <= SE_SMALL) {
             const long row = (long)y * W + tx0;                      // the same for all lanes of the wave
-            se_pixel_regs(a.a + row, a.b + row, lane, C, a.prob ? a.prob + row : nullptr, HW, b1, b2, be);
+            se_pixel_regs(a.a + row, a.b + row, lane, C, a.prob ? a.prob + row : nullptr, HW, b1, b2, be, me);
         } else if (ident) {
-            se_pixel_any<true>(a.a + px, a.b + px, HW, 0, 0, 0, 0, 0.f, 0.f, C, prob, HW, b1, b2, be);
+            se_pixel_any<true>(a.a + px, a.b + px, HW, 0, 0, 0, 0, 0.f, 0.f, C, prob, HW, b1, b2, be, me);
         } else {
             int y0, y1, x0, x1;
             float ly, lx;
@@ -253,9 +276,9 @@ __global__ __launch_bounds__(SE_THREADS) void seg_ens_kernel(const SegEnsArgs a)
             se_src(x, sx, w, x0, x1, lx);
             if (staged) {
                 const int r0 = (y0 - fy0) * fw - fx0, r1 = (y1 - fy0) * fw - fx0, ps = 2 * Cp;
-                se_pixel_lds(st, Cp, (r0 + x0) * ps, (r0 + x1) * ps, (r1 + x0) * ps, (r1 + x1) * ps, ly, lx, C, prob, HW, b1, b2, be);
+                se_pixel_lds(st, Cp, (r0 + x0) * ps, (r0 + x1) * ps, (r1 + x0) * ps, (r1 + x1) * ps, ly, lx, C, prob, HW, b1, b2, be, me);
             } else {
-                se_pixel_any<false>(a.a, a.b, hw, y0 * w + x0, y0 * w + x1, y1 * w + x0, y1 * w + x1, ly, lx, C, prob, HW, b1, b2, be);
+                se_pixel_any<false>(a.a, a.b, hw, y0 * w + x0, y0 * w + x1, y1 * w + x0, y1 * w + x1, ly, lx, C, prob, HW, b1, b2, be, me);
             }
         }
         if (a.pred) a.pred[px] = be;
@@ -297,7 +320,194 @@ __global__ __launch_bounds__(SE_THREADS) void seg_ens_kernel(const SegEnsArgs a)
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------------- dupl_seg_decide
+// The tail of a label-less run (tools/predict) on the same tiles: winner, its confidence, rejection under min_conf, the label map as
+// bytes and the per-label pixel counts and confidence sums.  Two students take the ensemble's own pixel functions above (the label
+// and conf are the bits of seg_ens_kernel's pred and prob); one student needs two sweeps only -- maximum, partition sum -- since
+// conf = softmax(u)[argmax u] = 1 / sum exp(u - max); probabilities (what DenseCRF returns) need one.
+enum { SD_ONE = 0, SD_TWO = 1, SD_PROB = 2 };
+constexpr int SD_SLOTS = 256;            // DUPL_SEG_DECIDE_MAX_C labels + the rejected pixels
+
+struct SegDecArgs {
+    const float* a;
+    const float* b;
+    float* conf;
+    unsigned char* label;
+    unsigned long long* stats;
+    int C, h, w, H, W;
+    int mode, ignore;
+    float min_conf;
+    int stage_cap, tiles_x, ntiles;
+};
+
+// IDENT: q points at the pixel itself, channel stride ps; otherwise at channel 0 of the source, ps the plane stride, o00 .. o11 the taps
+template <bool IDENT>
+__device__ __forceinline__ void sd_pixel_one(const float* q, long ps, int o00, int o01, int o10, int o11, float ly, float lx, int C,
+                                             int& best, float& conf) {
+    auto val = [&](int c) -> float {
+        const float* p = q + (long)c * ps;
+        if (IDENT) return p[0];
+        return se_tap(p[o00], p[o01], p[o10], p[o11], ly, lx);
+    };
+    float m = -INFINITY;
+    best = 0;
+    for (int c = 0; c < C; ++c) {
+        const float u = val(c);
+        if (u > m) { m = u; best = c; }
+    }
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += (double)se_exp(val(c) - m);
+    conf = 1.f / (float)s;                     // the winner's exp is exactly 1
+}
+
+// Identity, C <= SE_SMALL, one student (the VOC form): as se_pixel_regs, the wave's row segment is read once and stays in registers
+// through both sweeps.  The same sums in the same order as sd_pixel_one: the same bits.
+__device__ __forceinline__ void sd_pixel_one_regs(const float* __restrict__ r, int lane, int C, long HW, int& best, float& conf) {
+    float u[SE_SMALL];
+#pragma unroll
+    for (int j = 0; j < SE_SMALL; ++j) u[j] = j < C ? r[(long)j * HW + lane] : -INFINITY;
+    float m = -INFINITY;
+    best = 0;
+#pragma unroll
+    for (int j = 0; j < SE_SMALL; ++j)
+        if (u[j] > m) { m = u[j]; best = j; }
+    double s = 0.0;
+#pragma unroll
+    for (int j = 0; j < SE_SMALL; ++j) s += (double)se_exp(u[j] - m);      // the pad's exp is 0
+    conf = 1.f / (float)s;
+}
+
+// probabilities at the output size: v = a, or the mean of a and b; the winner and its value
+__device__ __forceinline__ void sd_pixel_prob(const float* q1, const float* q2, long ps, int C, int& best, float& conf) {
+    float m = -INFINITY;
+    best = 0;
+    for (int c = 0; c < C; ++c) {
+        const float v = q2 ? 0.5f * (q1[(long)c * ps] + q2[(long)c * ps]) : q1[(long)c * ps];
+        if (v > m) { m = v; best = c; }
+    }
+    conf = m;
+}
+
+__global__ __launch_bounds__(SE_THREADS) void seg_decide_kernel(const SegDecArgs a) {
+    extern __shared__ __align__(16) unsigned int se_lds[];
+    __shared__ unsigned int s_cnt[SD_SLOTS];
+    __shared__ unsigned long long s_sum[SD_SLOTS];
+    float* st = reinterpret_cast<float*>(se_lds);
+    const int tid = threadIdx.x, C = a.C, H = a.H, W = a.W, h = a.h, w = a.w;
+    const int lane = tid & 63, wrow = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int Cp = (C + 3) & ~3;
+    const bool want_stats = a.stats != nullptr;
+    if (want_stats) {
+        for (int i = tid; i <= C; i += SE_THREADS) { s_cnt[i] = 0u; s_sum[i] = 0ull; }
+        __syncthreads();
+    }
+    const bool ident = h == H && w == W;
+    const float sy = bil_scale(h, H, false), sx = bil_scale(w, W, false);
+    const long HW = (long)H * W, hw = (long)h * w;
+    for (int t = blockIdx.x; t < a.ntiles; t += gridDim.x) {
+        const int ty0 = (t / a.tiles_x) * SE_TH, tx0 = (t % a.tiles_x) * SE_TW;
+        const int x = tx0 + lane, y = ty0 + wrow;
+        const bool live = x < W && y < H;
+        int fy0 = 0, fx0 = 0, fw = 0;
+        bool staged = false;
+        if (a.mode == SD_TWO && !ident) staged = se_stage_tile(a.a, a.b, st, tid, ty0, tx0, C, h, w, H, W, sy, sx, a.stage_cap, fy0, fx0, fw);
+        const long px = (long)y * W + x;
+        int win = 0;
+        float cf = 0.f;
+        if (live) {                            // the lanes off the grid stay in step: the epilogue shuffles across the wave
+            int y0 = 0, y1 = 0, x0 = 0, x1 = 0;
+            float ly = 0.f, lx = 0.f;
+            if (!ident) {
+                se_src(y, sy, h, y0, y1, ly);
+                se_src(x, sx, w, x0, x1, lx);
+            }
+            int b1, b2;
+            if (a.mode == SD_PROB) {
+                sd_pixel_prob(a.a + px, a.b ? a.b + px : nullptr, HW, C, win, cf);
+            } else if (a.mode == SD_ONE) {
+                if (ident && C <= SE_SMALL) sd_pixel_one_regs(a.a + ((long)y * W + tx0), lane, C, HW, win, cf);
+                else if (ident) sd_pixel_one<true>(a.a + px, HW, 0, 0, 0, 0, 0.f, 0.f, C, win, cf);
+                else sd_pixel_one<false>(a.a, hw, y0 * w + x0, y0 * w + x1, y1 * w + x0, y1 * w + x1, ly, lx, C, win, cf);
+            } else if (ident && C <= SE_SMALL) {
+                const long row = (long)y * W + tx0;
+                se_pixel_regs(a.a + row, a.b + row, lane, C, nullptr, HW, b1, b2, win, cf);
+            } else if (ident) {
+                se_pixel_any<true>(a.a + px, a.b + px, HW, 0, 0, 0, 0, 0.f, 0.f, C, nullptr, HW, b1, b2, win, cf);
+            } else if (staged) {
+                const int r0 = (y0 - fy0) * fw - fx0, r1 = (y1 - fy0) * fw - fx0, ps = 2 * Cp;
+                se_pixel_lds(st, Cp, (r0 + x0) * ps, (r0 + x1) * ps, (r1 + x0) * ps, (r1 + x1) * ps, ly, lx, C, nullptr, HW, b1, b2, win, cf);
+            } else {
+                se_pixel_any<false>(a.a, a.b, hw, y0 * w + x0, y0 * w + x1, y1 * w + x0, y1 * w + x1, ly, lx, C, nullptr, HW, b1, b2, win, cf);
+            }
+            if (a.conf) a.conf[px] = cf;
+        }
+        const bool rej = cf < a.min_conf;
+        if (a.label) {
+            // four labels to a word where the word lies inside this wave's row segment; the row ends (W is arbitrary) byte by byte
+            const unsigned int lab = live ? (unsigned int)(rej ? a.ignore : win) : 0u;
+            const unsigned int l1 = __shfl_down(lab, 1, 64), l2 = __shfl_down(lab, 2, 64), l3 = __shfl_down(lab, 3, 64);
+            if (live) {
+                unsigned char* p = a.label + px;
+                const int k = (int)(reinterpret_cast<unsigned long long>(p) & 3ull);
+                const bool full = lane >= k && lane - k + 3 < 64 && x - k + 3 < W;
+                if (!full) *p = (unsigned char)lab;
+                else if (k == 0) *reinterpret_cast<unsigned int*>(p) = lab | (l1 << 8) | (l2 << 16) | (l3 << 24);
+            }
+        }
+        if (want_stats) {
+            // neighbouring pixels mostly share a label: a wave whose 64 pixels agree adds once; otherwise a pixel at a time
+            const int slot = live ? (rej ? C : win) : -1;
+            long long q = live ? (long long)rintf(cf * 16777216.f) : 0ll;
+            const int first = __builtin_amdgcn_readfirstlane(slot);
+            if (__ballot(slot != first) == 0ull) {
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
+                if (lane == 0 && first >= 0) {
+                    atomicAdd(&s_cnt[first], 64u);
+                    atomicAdd(&s_sum[first], (unsigned long long)q);
+                }
+            } else if (live) {
+                atomicAdd(&s_cnt[slot], 1u);
+                atomicAdd(&s_sum[slot], (unsigned long long)q);
+            }
+        }
+    }
+    if (want_stats) {
+        __syncthreads();
+        for (int i = tid; i <= C; i += SE_THREADS) {
+            if (s_cnt[i]) {
+                atomicAdd(&a.stats[i], (unsigned long long)s_cnt[i]);
+                atomicAdd(&a.stats[C + 1 + i], s_sum[i]);
+            }
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int dupl_seg_decide(const dupl_seg_decide_desc* d, dupl_stream_t stream) {
+    if (!d || d->struct_size != sizeof(dupl_seg_decide_desc)) return DUPL_ERR_ARG;
+    if (!d->a) return DUPL_ERR_ARG;
+    if (d->C < 1 || d->C > DUPL_SEG_DECIDE_MAX_C || d->h <= 0 || d->w <= 0 || d->H <= 0 || d->W <= 0) return DUPL_ERR_ARG;
+    if ((long)d->H * d->W > 0x7ffffff0L || (long)d->h * d->w > 0x7ffffff0L) return DUPL_ERR_ARG;
+    if (d->is_prob && (d->h != d->H || d->w != d->W)) return DUPL_ERR_ARG;
+    if (d->ignore_index < 0 || d->ignore_index > 255 || d->reserved0 != 0) return DUPL_ERR_ARG;
+    if (!d->conf && !d->label && !d->stats) return DUPL_ERR_ARG;
+    SegDecArgs a;
+    a.a = d->a; a.b = d->b; a.conf = d->conf; a.label = d->label; a.stats = (unsigned long long*)d->stats;
+    a.C = d->C; a.h = d->h; a.w = d->w; a.H = d->H; a.W = d->W;
+    a.mode = d->is_prob ? SD_PROB : (d->b ? SD_TWO : SD_ONE);
+    a.ignore = d->ignore_index;
+    a.min_conf = d->min_conf;
+    a.stage_cap = a.mode == SD_TWO ? se_stage_floats(d->C, d->h, d->w, d->H, d->W) : 0;
+    a.tiles_x = (d->W + SE_TW - 1) / SE_TW;
+    const long ntiles = (long)a.tiles_x * ((d->H + SE_TH - 1) / SE_TH);
+    if (ntiles > 0x7fffffffL) return DUPL_ERR_ARG;
+    a.ntiles = (int)ntiles;
+    const long grid = ntiles < 2048 ? ntiles : 2048;
+    DUPL_LAUNCH(seg_decide_kernel, dim3((unsigned)grid), dim3(SE_THREADS), sizeof(float) * (size_t)a.stage_cap, (hipStream_t)stream, a);
+    return dupl_launch_status();
+}
 
 extern "C" int dupl_seg_ensemble(const dupl_seg_ensemble_desc* d, dupl_stream_t stream) {
     if (!d || d->struct_size != sizeof(dupl_seg_ensemble_desc)) return DUPL_ERR_ARG;
@@ -314,16 +524,7 @@ extern "C" int dupl_seg_ensemble(const dupl_seg_ensemble_desc* d, dupl_stream_t 
     const int nb = 3 * d->C * d->C;
     a.priv = d->hist && nb <= SE_BINS;
     a.bin_words = a.priv ? (((nb + 1) / 2 + 3) & ~3) : 0;               // the stage behind it stays 16-byte aligned
-    a.stage_cap = 0;
-    if (d->h != d->H || d->w != d->W) {
-        // an upper bound of a tile's footprint; the kernel checks every tile's own footprint against stage_cap
-        const double sy = (double)d->h / d->H, sx = (double)d->w / d->W;
-        long fh = (long)((SE_TH - 1) * sy) + 4, fw = (long)((SE_TW - 1) * sx) + 4;
-        if (fh > d->h) fh = d->h;
-        if (fw > d->w) fw = d->w;
-        const long need = fh * fw * 2 * ((d->C + 3) & ~3);
-        a.stage_cap = need <= SE_STAGE ? (int)need : 0;
-    }
+    a.stage_cap = se_stage_floats(d->C, d->h, d->w, d->H, d->W);
     a.tiles_x = (d->W + SE_TW - 1) / SE_TW;
     const long ntiles = (long)a.tiles_x * ((d->H + SE_TH - 1) / SE_TH);
     if (ntiles > 0x7fffffffL) return DUPL_ERR_ARG;

@@ -1142,3 +1142,103 @@ def seg_ensemble(a: Tensor, b: Tensor, size, gt: Optional[Tensor] = None, hist: 
                              pred=_p(pred), prob=_p(prob))
     L().dupl_seg_ensemble(ctypes.byref(d), _stream())
     return pred, prob
+
+
+# ------------------------------------------------------------------------------------------ label-less inference (tools/predict)
+def seg_decide(a: Tensor, b: Optional[Tensor] = None, size=None, *, is_prob: bool = False, min_conf: float = 0.0,
+               ignore_index: int = 255, stats: Optional[Tensor] = None, want_label: bool = True, want_conf: bool = True):
+    """The tail after the seg logits of one image, one pass over the (H,W) = size grid (csrc/seg_ens.hip::seg_decide_kernel).
+    a (and b, the second student): (C,h,w) or (1,C,h,w) logits, up-sampled as ops.seg_ensemble does (size None: (h,w)); one
+    student: winner = argmax_c u, conf = softmax_c(u)[winner]; two: e = (softmax(u_1) + softmax(u_2)) / 2, winner = argmax_c e,
+    conf = e[winner].  is_prob: a (and b) are probabilities at the output size already (DenseCRF's result): their values (their
+    mean) are taken as they are.
+      label (H,W) uint8 = winner, or ignore_index where conf < min_conf;   conf (H,W) fp32;
+      stats (2, C+1) int64 += [pixels per label, slot C = rejected; sum of rint(conf * 2^24) over the same pixels].
+    Returns (label or None, conf or None); stats is updated in place."""
+    if a.dim() == 4:
+        assert a.shape[0] == 1 and (b is None or b.shape[0] == 1), "seg_decide takes one image per call"
+        a, b = a[0], (b[0] if b is not None else None)
+    assert a.dim() == 3 and (b is None or a.shape == b.shape), f"a, b: (C,h,w) of equal shape, got {tuple(a.shape)}"
+    C, h, w = a.shape
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if not 1 <= C <= _lib.SEG_DECIDE_MAX_C:
+        raise ValueError(f"seg_decide takes 1 .. {_lib.SEG_DECIDE_MAX_C} channels, got {C}")
+    if is_prob and (h, w) != (H, W):
+        raise ValueError(f"seg_decide(is_prob=True) takes probabilities at the output size {(H, W)}, got {(h, w)}")
+    if not 0 <= int(ignore_index) <= 255:
+        raise ValueError(f"ignore_index must be 0 .. 255, got {ignore_index}")
+    a = _chk(a.contiguous())
+    b = _chk(b.contiguous()) if b is not None else None
+    dev = a.device
+    if stats is not None:
+        assert stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and tuple(stats.shape) == (2, C + 1), \
+            f"stats must be (2, C + 1) int64, got {tuple(stats.shape)}"
+    if stats is None and not want_label and not want_conf:
+        raise ValueError("seg_decide: nothing asked for (stats, want_label, want_conf)")
+    label = torch.empty((H, W), device=dev, dtype=torch.uint8) if want_label else None
+    conf = torch.empty((H, W), device=dev, dtype=torch.float32) if want_conf else None
+    d = _lib.SegDecideDesc(C=C, h=h, w=w, H=H, W=W, is_prob=int(bool(is_prob)), ignore_index=int(ignore_index),
+                           min_conf=float(min_conf), a=a.data_ptr(), b=_p(b), conf=_p(conf), label=_p(label), stats=_p(stats))
+    L().dupl_seg_decide(ctypes.byref(d), _stream())
+    return label, conf
+
+
+def seg_paint(label: Tensor, palette: Tensor, image: Optional[Tensor] = None, *, alpha256: int = 154, tint_background: bool = False,
+              contour: bool = False, contour_rgb=(255, 255, 255)) -> Tensor:
+    """label (H,W) uint8, palette (256,3) uint8, image (H,W,3) uint8 or None -> (H,W,3) uint8 (csrc/seg_render.hip), integers only:
+    palette[label] without image, else (image * (256 - alpha256) + palette[label] * alpha256 + 128) >> 8 where pixels of label 0
+    keep the image unless tint_background; with contour a pixel whose label differs from its right or lower neighbour's gets
+    contour_rgb."""
+    for t, name in ((label, "label"), (palette, "palette")) + (((image, "image"),) if image is not None else ()):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous(), f"{name}: a contiguous uint8 device tensor"
+    assert label.dim() == 2 and tuple(palette.shape) == (256, 3), "label (H,W), palette (256,3)"
+    H, W = label.shape
+    assert image is None or tuple(image.shape) == (H, W, 3), f"image must be {(H, W, 3)}"
+    if not 0 <= int(alpha256) <= 256:
+        raise ValueError(f"alpha256 must be 0 .. 256, got {alpha256}")
+    out = torch.empty((H, W, 3), device=label.device, dtype=torch.uint8)
+    d = _lib.SegPaintDesc(H=H, W=W, alpha256=int(alpha256), tint_background=int(bool(tint_background)), contour=int(bool(contour)),
+                          contour_rgb=(ctypes.c_uint8 * 3)(*[int(v) for v in contour_rgb]), label=label.data_ptr(), image=_p(image),
+                          palette=palette.data_ptr(), out=out.data_ptr())
+    L().dupl_seg_paint(ctypes.byref(d), _stream())
+    return out
+
+
+def _window_table(origins, name: str):
+    org = np.ascontiguousarray(np.asarray(origins, dtype=np.int32).reshape(-1, 2))
+    if not 1 <= len(org) <= _lib.WINDOW_MAX:
+        raise ValueError(f"{name} takes 1 .. {_lib.WINDOW_MAX} windows per call, got {len(org)}")
+    return org
+
+
+def window_gather(x: Tensor, Hs: int, Ws: int, origins, wh: int, ww: int) -> Tensor:
+    """x (1,3,h,w) -> (2 nW, 3, wh, ww): the windows at origins [(r0, c0), ...] of the image resized to (Hs,Ws), then the same
+    coordinates of its horizontal flip; the bits of resize_bilinear(x, Hs, Ws, flip_cat=True)[:, :, r0:r0+wh, c0:c0+ww] without
+    the resized image in memory (csrc/seg_render.hip)."""
+    assert x.dim() == 4 and x.shape[0] == 1 and x.shape[1] == 3, f"x: (1,3,h,w), got {tuple(x.shape)}"
+    x = _chk(x.contiguous())
+    org = _window_table(origins, "window_gather")
+    if (org < 0).any() or (org[:, 0] + wh > Hs).any() or (org[:, 1] + ww > Ws).any():
+        raise ValueError(f"window_gather: a {wh} x {ww} window lies outside the {Hs} x {Ws} image")
+    out = torch.empty((2 * len(org), 3, int(wh), int(ww)), device=x.device, dtype=torch.float32)
+    d = _lib.WindowGatherDesc(h=x.shape[2], w=x.shape[3], Hs=int(Hs), Ws=int(Ws), nW=len(org), wh=int(wh), ww=int(ww),
+                              x=x.data_ptr(), origins=org.ctypes.data, out=out.data_ptr())
+    L().dupl_window_gather(ctypes.byref(d), _stream())
+    return out
+
+
+def window_merge(logits: Tensor, origins, hs: int, ws: int) -> Tensor:
+    """logits (2 nW, C, wth, wtw) of the windows at origins [(r0, c0), ...] (tokens) -> canvas (2, C, hs, ws): per element the
+    covering windows added in ascending index in fp32 and divided once by their number (csrc/seg_render.hip); the first half
+    from the windows of the image, the second from those of its flip -- what msc_seg_accum_ consumes."""
+    logits = _chk(logits.contiguous())
+    org = _window_table(origins, "window_merge")
+    assert logits.dim() == 4 and logits.shape[0] == 2 * len(org), f"logits: (2 nW, C, wth, wtw) for {len(org)} windows, got {tuple(logits.shape)}"
+    _, C, wth, wtw = logits.shape
+    if (org < 0).any() or (org[:, 0] + wth > hs).any() or (org[:, 1] + wtw > ws).any():
+        raise ValueError(f"window_merge: a {wth} x {wtw} window lies outside the {hs} x {ws} canvas")
+    out = torch.empty((2, C, int(hs), int(ws)), device=logits.device, dtype=torch.float32)
+    d = _lib.WindowMergeDesc(C=C, hs=int(hs), ws=int(ws), nW=len(org), wth=wth, wtw=wtw, logits=logits.data_ptr(),
+                             origins=org.ctypes.data, canvas=out.data_ptr())
+    L().dupl_window_merge(ctypes.byref(d), _stream())
+    return out

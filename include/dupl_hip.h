@@ -690,6 +690,85 @@ typedef struct dupl_seg_ensemble_desc {
 } dupl_seg_ensemble_desc;
 int dupl_seg_ensemble(const dupl_seg_ensemble_desc* d, dupl_stream_t stream);
 
+/* ------------------------------------------------------------------ label-less inference (tools/predict; csrc/seg_ens.hip, csrc/seg_render.hip)
+ * Beyond the reference, which only scores against a ground truth.  dupl_seg_decide is the tail after the seg logits of ONE image in
+ * one pass over the (H,W) grid.  Per pixel, with u_s as in dupl_seg_ensemble (the same tap arithmetic, the values themselves when
+ * (h,w) == (H,W)):
+ *   one student  (b NULL):  winner = argmax_c u (first maximum wins), conf = softmax_c(u)[winner];
+ *   two students:           e = (softmax(u_1) + softmax(u_2)) / 2 -- the bits of dupl_seg_ensemble's prob --, winner = argmax_c e,
+ *                           conf = e[winner];
+ *   is_prob != 0:           a (and b) hold probabilities at (H,W) already (what DenseCRF returns): v = a, or (a + b) / 2;
+ *                           winner = argmax_c v, conf = v[winner].
+ * label = winner, or ignore_index where conf < min_conf (the fp32 conf this call computes).  stats (2, C+1) int64 is ADDED to:
+ * row 0 the pixels per output label with slot C for the rejected ones, row 1 the sum of (int64)rintf(conf * 2^24) over the same
+ * pixels (conf <= 1, so the product is exact and rintf rounds halves to even): integer atomics only, bit-reproducible.
+ * Every output is optional, at least one is required. */
+#define DUPL_SEG_DECIDE_MAX_C 255
+typedef struct dupl_seg_decide_desc {
+    uint32_t struct_size;        /* sizeof(dupl_seg_decide_desc), checked */
+    int32_t C, h, w;             /* a, b: (C,h,w) fp32; 1 <= C <= DUPL_SEG_DECIDE_MAX_C */
+    int32_t H, W;                /* output grid */
+    int32_t is_prob;             /* != 0: the inputs are probabilities; requires (h,w) == (H,W) */
+    int32_t ignore_index;        /* 0 .. 255: the label of rejected pixels */
+    float min_conf;              /* pixels with conf < min_conf are rejected (0: none) */
+    int32_t reserved0;           /* 0 */
+    const float* a;              /* student 1 */
+    const float* b;              /* student 2; or NULL */
+    float* conf;                 /* (H,W); or NULL */
+    uint8_t* label;              /* (H,W); or NULL */
+    int64_t* stats;              /* (2, C+1); or NULL */
+} dupl_seg_decide_desc;
+int dupl_seg_decide(const dupl_seg_decide_desc* d, dupl_stream_t stream);
+
+/* Palette image / overlay of a label map, integer arithmetic only.  out (H,W,3) uint8:
+ *   image NULL:  palette[label];
+ *   otherwise:   (image * (256 - alpha256) + palette[label] * alpha256 + 128) >> 8; pixels of label 0 keep image when
+ *                tint_background == 0;
+ *   contour != 0: a pixel whose label differs from the label at (y, x+1) or (y+1, x), where those exist, gets contour_rgb. */
+typedef struct dupl_seg_paint_desc {
+    uint32_t struct_size;        /* sizeof(dupl_seg_paint_desc), checked */
+    int32_t H, W;
+    int32_t alpha256;            /* 0 .. 256 */
+    int32_t tint_background;     /* 0 / 1 */
+    int32_t contour;             /* 0 / 1 */
+    uint8_t contour_rgb[3];
+    uint8_t reserved0;           /* 0 */
+    const uint8_t* label;        /* (H,W) */
+    const uint8_t* image;        /* (H,W,3); or NULL */
+    const uint8_t* palette;      /* (256,3), device memory */
+    uint8_t* out;                /* (H,W,3) */
+} dupl_seg_paint_desc;
+int dupl_seg_paint(const dupl_seg_paint_desc* d, dupl_stream_t stream);
+
+/* Sliding windows.  dupl_window_gather: out (2 nW, 3, wh, ww); entry i < nW is the window at origins[i] = (r0, c0) of the bilinear
+ * (align_corners False) resize of x (1,3,h,w) to (Hs,Ws), entry nW + i the same coordinates of its horizontal flip -- the bits of
+ * dupl_resize_bilinear(flip_cat = 1)[:, :, r0:r0+wh, c0:c0+ww]; the resized image is never written.  Every window must lie inside
+ * (Hs,Ws).  dupl_window_merge: logits (2 nW, C, wth, wtw) of those windows, origins in tokens, -> canvas (2, C, hs, ws): per canvas
+ * element the covering windows are added in ascending index in fp32 and divided once by their number (no atomics: bit-reproducible);
+ * every window must lie inside (hs,ws); an element that no window covers is 0.  The origins are read on the HOST, at the call (they
+ * are checked there and travel to the kernel with its arguments): 1 <= nW <= DUPL_WINDOW_MAX. */
+#define DUPL_WINDOW_MAX 256
+typedef struct dupl_window_gather_desc {
+    uint32_t struct_size;        /* sizeof(dupl_window_gather_desc), checked */
+    int32_t h, w;                /* x: (1,3,h,w) fp32 */
+    int32_t Hs, Ws;              /* the scaled image the windows are cut from */
+    int32_t nW, wh, ww;          /* windows and their size in pixels */
+    const float* x;
+    const int32_t* origins;      /* (nW,2) (r0,c0) in pixels of (Hs,Ws), host memory */
+    float* out;                  /* (2 nW, 3, wh, ww) */
+} dupl_window_gather_desc;
+int dupl_window_gather(const dupl_window_gather_desc* d, dupl_stream_t stream);
+typedef struct dupl_window_merge_desc {
+    uint32_t struct_size;        /* sizeof(dupl_window_merge_desc), checked */
+    int32_t C;                   /* channels of the logits */
+    int32_t hs, ws;              /* the canvas, in tokens */
+    int32_t nW, wth, wtw;        /* windows and their size in tokens */
+    const float* logits;         /* (2 nW, C, wth, wtw) */
+    const int32_t* origins;      /* (nW,2) (r0,c0) in tokens, host memory */
+    float* canvas;               /* (2, C, hs, ws) */
+} dupl_window_merge_desc;
+int dupl_window_merge(const dupl_window_merge_desc* d, dupl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,9 +1,13 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd | seg_render | predict
 `crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81.
 `cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces.
 `seg_ensemble` (only when named) times the fused ensemble tail of tools/eval_seg --ensemble 1 (ops.seg_ensemble) against the composition
 of existing ops that yields the same matrices, at the VOC and the COCO form.
+`seg_render` (only when named; then nothing else runs) times ops.seg_decide against the composition of existing ops that yields the
+same label and confidence (VOC and COCO form, one and two students) and ops.seg_paint against the host palette-and-blend.
+`predict` (only when named; then nothing else runs) times tools/predict on one synthetic 1024 x 2048 image, ViT-B, whole image against
+sliding windows, with the peak device memory of each.
 `backbone` (only when named; then nothing else runs) times one phase-B training step at VOC 448^2, 4 images, two student streams
 for every registered --backbone, or for the names that follow it: bench.py's own workload and timed region (bench.Workload.measure:
 warm-up steps, then K steps between synchronisations), so the deit_base_patch16_224 row is bench.py's figure.
@@ -160,6 +164,98 @@ def seg_ensemble_bench(dev, g):
                   f"({t_h / t_f:.1f}x fused)")
 
 
+def seg_render_bench(dev, g):
+    """ops.seg_decide (label + conf + stats, one launch) against the composition of existing ops that yields the same label and conf
+    -- resize_bilinear -> softmax (x 2 and the mean with two students) -> max -> argmax_channels -> uint8 --, per call at batch 1, at
+    the VOC form (375 x 500, C = 21, logits at label size) and the COCO form (480 x 640, C = 81, from 28 x 28), one and two students;
+    and ops.seg_paint against the host palette lookup and blend it replaces (label and image already on the host, the result left
+    there: the device -> host copies the host path needs on top are not counted)."""
+    import numpy as np
+    from dupl_amd.utils import imutils
+    for name, C, h, w, H, W in (("VOC", 21, 375, 500, 375, 500), ("COCO", 81, 28, 28, 480, 640)):
+        def logits():            # smooth at label size, as seg_ensemble_bench's: predictions come in regions
+            if h <= 32:
+                return (torch.randn((1, C, h, w), generator=g) * 3).to(dev)
+            up = torch.nn.functional.interpolate(torch.randn((1, C, 24, 32), generator=g) * 3, size=(h, w), mode="bilinear", align_corners=False)
+            return (up + 0.05 * torch.randn((1, C, h, w), generator=g)).contiguous().to(dev)
+
+        a, b = logits(), logits()
+        stats = torch.zeros((2, C + 1), device=dev, dtype=torch.int64)
+
+        def composed(two):
+            p = torch.softmax(ops.resize_bilinear(a, H, W), 1)
+            if two:
+                p = (p + torch.softmax(ops.resize_bilinear(b, H, W), 1)) * 0.5
+                label = ops.argmax_channels(p)[0]
+            else:
+                label = ops.upsample_argmax(a, H, W)[0] if (h, w) != (H, W) else ops.argmax_channels(a)[0]
+            return label.to(torch.uint8), p[0].max(0).values
+
+        for two in (False, True):
+            fused = lambda: ops.seg_decide(a, b if two else None, (H, W), min_conf=0.5, stats=stats)
+            rounds = [(timeit(fused, n=200), timeit(lambda: composed(two), n=50, warm=5)) for _ in range(2)]
+            floor = (2 if two else 1) * C * h * w * 4 + H * W * 5
+            for i, (t_f, t_c) in enumerate(rounds):
+                print(f"seg_decide {name} {H}x{W} C={C} from {h}x{w}, {'two students' if two else 'one student'}, round {i}: fused {t_f:.1f} us "
+                      f"({floor / t_f / 1e6:.3f} TB/s of its {floor / 1e6:.2f} MB floor); composed (no stats) {t_c:.1f} us ({t_c / t_f:.1f}x fused)")
+    pal_np = imutils.colormap()
+    pal = torch.from_numpy(pal_np).to(dev)
+    for H, W in ((375, 500), (1024, 2048)):
+        lab_np = np.repeat(np.repeat(torch.randint(0, 21, (H // 25 + 1, W // 25 + 1), generator=g).numpy().astype(np.uint8), 25, 0), 25, 1)[:H, :W].copy()
+        img_np = torch.randint(0, 256, (H, W, 3), generator=g).numpy().astype(np.uint8)
+        lab, img = torch.from_numpy(lab_np).to(dev), torch.from_numpy(img_np).to(dev)
+
+        def host():
+            out = (img_np.astype(np.int32) * 102 + pal_np[lab_np].astype(np.int32) * 154 + 128) >> 8
+            return np.where((lab_np == 0)[..., None], img_np, out).astype(np.uint8)
+
+        import time
+        host()
+        t0 = time.perf_counter()
+        for _ in range(5):
+            host()
+        t_h = (time.perf_counter() - t0) / 5 * 1e6
+        assert np.array_equal(ops.seg_paint(lab, pal, img, alpha256=154).cpu().numpy(), host())
+        for i in range(2):
+            t_o = timeit(lambda: ops.seg_paint(lab, pal, img, alpha256=154), n=200)
+            t_c = timeit(lambda: ops.seg_paint(lab, pal, img, alpha256=154, contour=True), n=200)
+            t_p = timeit(lambda: ops.seg_paint(lab, pal), n=200)
+            print(f"seg_paint {H}x{W}, round {i}: overlay {t_o:.1f} us ({H * W * 7 / t_o / 1e6:.3f} TB/s of 7 B/px), with contours {t_c:.1f} us, "
+                  f"palette only {t_p:.1f} us; host numpy palette + blend {t_h:.0f} us ({t_h / t_o:.0f}x)")
+
+
+def predict_bench(argv):
+    """tools/predict on one synthetic 1024 x 2048 image, ViT-B (seeded random weights), scales 1.0 / 1.5 / 1.25: the whole image per
+    scale against sliding windows (window=448 stride=320 window_batch=8), ms per image and peak device memory.
+        python tools/op_bench.py predict [H=1024] [W=2048] [window=448] [stride=320] [window_batch=8] [n=3] [backbone=vit_base_patch16_224]"""
+    import numpy as np
+    from dupl_amd.model.model_dupl import siamese_network
+    from dupl_amd.tools import predict
+    opts = dict(a.split("=", 1) for a in argv if "=" in a)
+    H, W, n = int(opts.get("H", 1024)), int(opts.get("W", 2048)), int(opts.get("n", 3))
+    window, stride, wb = int(opts.get("window", 448)), int(opts.get("stride", 320)), int(opts.get("window_batch", 8))
+    backbone = opts.get("backbone", "vit_base_patch16_224")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    model = siamese_network(backbone=backbone, num_classes=21, pretrained=False, aux_layer=-3).to(dev).eval()
+    image = np.random.RandomState(0).randint(0, 256, size=(H, W, 3)).astype(np.uint8)
+    arms = [("windows", dict(window=window, stride=stride, window_batch=wb))]
+    if opts.get("whole", "1") == "1":
+        arms.append(("whole image", dict(window=0)))
+    for name, kw in arms:
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        try:
+            r = predict.predict_image(model, image, branch="ens", **kw)          # warm-up: allocations, the pos-embed grids
+            torch.cuda.synchronize()
+            ms = timeit(lambda: predict.predict_image(model, image, branch="ens", **kw), n=n, warm=0) / 1e3
+        except (RuntimeError, torch.OutOfMemoryError) as e:
+            print(f"predict {backbone} {H}x{W} {name}: could not run: {type(e).__name__}: {str(e).splitlines()[0][:200]}")
+            continue
+        print(f"predict {backbone} {H}x{W} {name} {kw}: {ms:.1f} ms / image, windows per scale {r['windows']}, "
+              f"peak device memory {torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB")
+
+
 def backbone_bench(argv):
     """ms / step and img / s of one phase-B step (VOC, 448^2, 4 images on one GPU, two streams) per backbone."""
     import os
@@ -237,6 +333,10 @@ def main():
         return backbone_bench(sys.argv[1:])
     if "nograd" in sys.argv[1:]:
         return nograd_bench(sys.argv[1:])
+    if "predict" in sys.argv[1:]:
+        return predict_bench(sys.argv[1:])
+    if "seg_render" in sys.argv[1:]:
+        return seg_render_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)

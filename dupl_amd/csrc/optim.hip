@@ -3,17 +3,25 @@
 #include "common.h"
 #include "../../include/dupl_hip.h"
 
+// Every rounding of the update is one operator below, and contraction is off for the code of this file, so none can be fused
+// away.  The __f*_rn spellings do not do that: without OCML_BASIC_ROUNDED_OPERATIONS hipcc's headers define __fmul_rn / __fsub_rn /
+// __fadd_rn as plain operators that carry the header's (contracting) mode into the caller, and __fsqrt_rn as the native 1-ulp
+// square root -- p * decay was fused into the final subtraction (one rounding where torch's mul_ + addcdiv_ have two) and
+// sqrt(v) was not correctly rounded.  The two fused multiply-adds are explicit; sqrtf and / are correctly rounded (hipcc's
+// default).  tests/test_adamw_gmm_kernels_gpu.py holds all four instantiations to tests/optim_ref.py bit for bit.
+#pragma clang fp contract(off)
+
 namespace {
 
 // every operation with its rounding written out: hipcc's fp contraction must not depend on the surrounding code (the two
 // instantiations of the kernel below differed in the last bit of m in their scalar tails)
 __device__ __forceinline__ void adamw_one(float& p, float g, float& m, float& v, float decay, float b1, float b2, float eps,
                                           float step_size, float bc2_sqrt) {
-    p = __fmul_rn(p, decay);                                              // p.mul_(1 - lr*wd)
-    m = __fmaf_rn(b1, m, __fmul_rn(1.f - b1, g));                          // exp_avg.lerp_(grad, 1-beta1)
-    v = __fmaf_rn(b2, v, __fmul_rn(__fmul_rn(1.f - b2, g), g));            // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
-    const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), bc2_sqrt), eps);
-    p = __fsub_rn(p, __fmul_rn(step_size, __fdiv_rn(m, denom)));
+    p = p * decay;                                                        // p.mul_(1 - lr*wd)
+    m = __builtin_fmaf(b1, m, (1.f - b1) * g);                            // exp_avg.lerp_(grad, 1-beta1)
+    v = __builtin_fmaf(b2, v, ((1.f - b2) * g) * g);                      // exp_avg_sq.mul_(b2).addcmul_(g, g, 1-b2)
+    const float denom = sqrtf(v) / bc2_sqrt + eps;
+    p = p - step_size * (m / denom);
 }
 
 // PLANES: the updated parameters also leave as the f16x3 operand planes of the next forward (format 0, or format 1 = w * 2^exp with
@@ -31,8 +39,8 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
         float4 pv = reinterpret_cast<float4*>(p)[i], mv = reinterpret_cast<float4*>(m)[i], vv = reinterpret_cast<float4*>(v)[i];
         float4 gv = reinterpret_cast<const float4*>(g)[i];
         if (GSCALE) {
-            gv.x = __fmul_rn(gv.x, grad_scale); gv.y = __fmul_rn(gv.y, grad_scale);
-            gv.z = __fmul_rn(gv.z, grad_scale); gv.w = __fmul_rn(gv.w, grad_scale);
+            gv.x = gv.x * grad_scale; gv.y = gv.y * grad_scale;
+            gv.z = gv.z * grad_scale; gv.w = gv.w * grad_scale;
             reinterpret_cast<float4*>(g)[i] = gv;
         }
         adamw_one(pv.x, gv.x, mv.x, vv.x, decay, b1, b2, eps, step_size, bc2_sqrt);
@@ -53,7 +61,7 @@ __global__ void adamw_kernel(float* __restrict__ p, float* __restrict__ g, float
         }
     }
     for (long i = n4 * 4 + (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += st) {
-        if (GSCALE) g[i] = __fmul_rn(g[i], grad_scale);
+        if (GSCALE) g[i] = g[i] * grad_scale;
         adamw_one(p[i], g[i], m[i], v[i], decay, b1, b2, eps, step_size, bc2_sqrt);
         if (PLANES) {
             if (plane_scale > 0.f) split_f32_u(p[i] * plane_scale, hi[i], lo[i]);

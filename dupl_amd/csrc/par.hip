@@ -217,7 +217,8 @@ extern "C" int dupl_par_affinity(const float* imgs, float* aff, const int32_t* d
 extern "C" int dupl_par_propagate(const float* aff, const float* in, float* out, const int32_t* job_img, const int32_t* job_K,
                                   const int32_t* dilations, int32_t ndil, int32_t njobs, int32_t Kmax, int32_t h, int32_t w,
                                   dupl_stream_t s) {
-    if (!aff || !in || !out || !job_img || !job_K || !dilations || ndil <= 0 || ndil * 8 > NN || njobs <= 0 || Kmax <= 0)
+    if (!aff || !in || !out || !job_img || !job_K || !dilations || ndil <= 0 || ndil * 8 > NN || njobs <= 0 || Kmax <= 0 ||
+        h <= 0 || w <= 0)
         return DUPL_ERR_ARG;
     const ParTables tb = make_tables(dilations, ndil);
     DUPL_LAUNCH(par_propagate_kernel, dim3((h * w + 255) / 256, (Kmax + 3) / 4, njobs), dim3(256), 0, (hipStream_t)s, aff,

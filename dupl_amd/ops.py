@@ -809,7 +809,9 @@ def par_affinity(imgs: Tensor, dilations: Sequence[int], pos_term: Tensor) -> Te
 
 
 def par_propagate(aff: Tensor, masks: Tensor, job_img: Tensor, job_K: Tensor, dilations: Sequence[int], num_iter: int) -> Tensor:
-    """masks [njobs, Kmax, h, w]; returns the propagated masks after num_iter ping-pong iterations."""
+    """masks [njobs, Kmax, h, w]; returns the propagated masks after num_iter ping-pong iterations (num_iter = 0: `masks` itself).
+    Job j uses aff[job_img[j]] and its first job_K[j] channels; channels >= job_K[j] of the result are UNSPECIFIED (the kernel neither
+    reads nor writes them, and the ping-pong buffer starts uninitialised): callers must not consume them."""
     njobs, Kmax, h, w = masks.shape
     nd = len(dilations)
     dil = (ctypes.c_int32 * nd)(*dilations)

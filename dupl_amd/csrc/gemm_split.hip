@@ -521,6 +521,75 @@ __device__ __forceinline__ void gemm16_epilogue_side(const dupl_gemm16_desc& p, 
         }
 }
 
+// The same side-buffer epilogue for the 4 x 4 blocks of 16x16x32 accumulators of a 64 x 64 wave tile (gemm_f16x3_km16_body; one set:
+// format 1).  Register e of block (i, j) is row 16 i + 4 (lane >> 4) + e, column 16 j + (lane & 15), so a pass of 8 rows takes a register
+// PAIR of every lane: pass (i, ep) = rows 16 i + 4 g + 2 ep + de (g = lane >> 4, de = 0, 1), parked in side row 2 g + de.  The b32 writes of
+// one register put the four lane groups two side rows apart at the same 16 columns: side rows 2 g, 2 g + 1 are stored rotated by 16 g
+// floats, so that one write instruction covers the 64 banks once; a row read back (b128, 16 lanes per row; b32, lane = column) is one
+// whole rotated row -- both stay conflict-free.  Everything a row then meets is epi16_quad / the ACC forms of gemm16_epilogue_side.
+template <bool ACC, bool ATOM, bool OVERW>
+__device__ __forceinline__ void gemm16_epilogue_side16(const dupl_gemm16_desc& p, f32x4 (&acc)[4][4], float* __restrict__ side, const int mw,
+                                                       const int nw, const int lane, float& amx) {
+    const int l15 = lane & 15, g = lane >> 4;
+    const float alpha = (p.alpha_dev ? *p.alpha_dev : 1.f) * (p.post_scale != 0.f ? p.post_scale : 1.f);
+    const Epi16 E = epi16_setup(p);
+    const int cl = l15 * 4, rl = g;
+    const int col = nw + cl;
+    const int nv = min(4, p.N - col);
+    float bv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (!ACC && p.bias && nv > 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+            if (c < nv) bv[c] = p.bias[col + c];
+    }
+    const bool want_aux = E.f_dgelu || E.f_rmask;
+    const bool pre_ld = !ACC && E.vec && nv == 4 && ((p.res != nullptr) != want_aux);
+    const float* pre_src = want_aux ? p.aux : p.res;
+    const int pre_ldm = want_aux ? p.ldaux : p.ldr;
+    auto tile_row = [](const int i, const int ep, const int s) { return 16 * i + 4 * (s >> 1) + 2 * ep + (s & 1); };   // of side row s
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int ep = 0; ep < 2; ++ep) {
+            f32x4 pq[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
+            if (pre_ld) {
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int row = mw + tile_row(i, ep, rl + 4 * k);
+                    if (row < p.M) pq[k] = *reinterpret_cast<const f32x4*>(pre_src + (size_t)row * pre_ldm + col);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int de = 0; de < 2; ++de) side[(2 * g + de) * 64 + ((j * 16 + l15 + 16 * g) & 63)] = acc[i][j][2 * ep + de] * alpha;
+            if constexpr (ACC) {
+                if (nw + lane < p.N) {
+                    const bool fresh = OVERW && (p.flags & DUPL_GEMM_C_FRESH);      // C = 0 + v: see gemm16_epilogue_side
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) {
+                        const int row = mw + tile_row(i, ep, r);
+                        if (row < p.M) {
+                            float* cp = p.C + (size_t)row * p.ldc + nw + lane;
+                            const float v = side[r * 64 + ((lane + 16 * (r >> 1)) & 63)];
+                            if (fresh) *cp = 0.f + v;
+                            else if constexpr (ATOM) unsafeAtomicAdd(cp, v);
+                            else *cp += v;
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int s = rl + 4 * k;
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(side + s * 64 + ((cl + 16 * (s >> 1)) & 63));
+                    const int row = mw + tile_row(i, ep, s);
+                    if (nv > 0 && row < p.M) epi16_quad(p, E, row, col, nv, t, bv, amx, pq[k], pre_ld ? (want_aux ? 2 : 1) : 0);
+                }
+            }
+        }
+}
+
 // ---- shared by the kernels below: the block tile's geometry, the block -> tile order, the piece DMA and the 32x32x16 fragment set
 // WM x WN: 32x32 MFMA tiles per wave; NWM x NWN: waves per block.  Block tile (32 WM NWM) x (32 WN NWN) x 32.
 template <int WM, int WN, int NWM, int NWN>
@@ -1724,9 +1793,342 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
                           NWM * NWN);
 }
 
-template <int WM, int WN, int NWM, int NWN, int WPS, bool SK, int ACC, bool AKM, bool BKM, int STAGES = 3>
+// ---------------------------------------------------------------------------------------------------------------------------
+// The same kernel body on v_mfma_f32_16x16x32_f16 (dupl_gemm16_desc.tile 26; gemm_f16x3_km_body is tile 24).  Unchanged: the template
+// switches, the 256 x 128 block tile on 8 waves of 64 x 64, the stage size and the ring (DMA STAGES k-tiles ahead, one counted vmcnt +
+// s_barrier per k-tile, vmcnt(0) in front of every other barrier), TileOrder, the stream-K slice rules, the k_valid clamp and every
+// descriptor field.  What changes, for the reason given at gemm_f16x3_ring16_kernel (the clock the chip holds under this loop):
+//   * 4 x 4 accumulators of f32x4 (the same 64 registers); a k-tile (32) is ONE MFMA k-step of 48 instructions, per accumulator hi.hi,
+//     hi.lo, lo.hi.  Only the order of the sums inside a k-tile differs from the 32x32x16 body (32 products per MFMA, not 2 x 16).
+//   * a k-contiguous operand lies as in gemm_f16x3_ring16_kernel: 16-row x 64-byte pieces, chunk j of row r at j ^ ((4 - (r >> 2)) & 3),
+//     a fragment = one ds_read_b128 of a whole piece.
+//   * a k-major operand lies in the [16 k][16 rows] 512-byte subtiles of split_frag.h (km16_*): plane image = subtile jj * (rows / 16) +
+//     dt, subtile row 4 g + i = k 8 g + 4 jj + i, rows 16 dt .. + 15; DMA piece q = subtiles 2 q, 2 q + 1 (64 contiguous bytes of 16
+//     k-rows).  A fragment = two ds_read_b64_tr_b16 (jj = 0, 1) at lane * 8: one contiguous subtile each, conflict-free.
+//   * schedule (gemm_f16x3_ring16_kernel's): the B fragments of a k-tile are held through it, the A fragments go in two phases of two
+//     row blocks, double-buffered -- 64 fragment registers.  Phase 0 runs over the reads of the tile's last B column block and of
+//     A(phase 1); then the counted wait and the barrier (tile t + 1 landed, every wave done reading tile t); phase 1 walks its column
+//     blocks in order and under block j reads A(phase 0) (j = 0) / B column block j - 1 (in place) of tile t + 1, and issues the DMA of
+//     tile t + STAGES into tile t's stage.  The stream is written out and pinned slot by slot as in gemm_f16x3_km_body; every wait for
+//     an inline-asm read carries the fragments it releases (split_frag.h).
+template <int WM, int WN, int NWM, int NWN, int WPS, bool SK, int ACC, bool AKM, bool BKM, int STAGES = 3, bool ONESHOT = false>
+__device__ __forceinline__ void gemm_f16x3_km16_body(const dupl_gemm16_desc& p, const int g_gm, const int bid0, const int grid) {
+    using G = RingGeom<WM, WN, NWM, NWN>;
+    constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB, STAGE = G::STAGE, PPW = G::PPW;
+    constexpr int APW = 2 * PA / NW;                       // this wave's first APW pieces belong to A, the rest to B
+    constexpr int RB = 2 * WM, CB = 2 * WN;                // 16 x 16 blocks of the wave tile
+    constexpr int NDA = AKM ? 2 : 1, NDB = BKM ? 2 : 1;    // LDS read instructions per fragment
+    constexpr int NLA = 4 * NDA, NLB = 2 * NDB;            // ... per A phase set (hi / lo of two row blocks) and per B column block (hi, lo)
+    constexpr int SIDE = NW * 2048;
+    static_assert(RB == 4 && CB == 4, "wave tile 64 x 64: two phases of two row blocks, the 4 x 4 side-buffer epilogue");
+    static_assert((2 * PA) % NW == 0, "pieces must divide over the waves, operand by operand");
+    static_assert(STAGES * STAGE + SIDE <= 160 * 1024, "LDS");
+    static_assert(!SK || ACC == 1, "stream-K pieces meet in atomics");
+    __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE + SIDE];
+    const int tid = threadIdx.x;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wm = wave / NWN, wn = wave % NWN;
+    const int nbm = (p.M + BM - 1) / BM, nbn = (p.N + BN - 1) / BN;
+    const int ntf = p.K / TBK;                    // k-steps of a whole tile, >= STAGES (host)
+    int nt = ntf;
+    const TileOrder<BM, BN> order(nbm, nbn, g_gm);
+
+    // ---- DMA plan: as gemm_f16x3_km_body, with the images described above
+    const int ka_valid = p.ka_valid > 0 ? p.ka_valid : p.K, kb_valid = p.kb_valid > 0 ? p.kb_valid : p.K;
+    // (bytes per k-row, read once: in the grouped kernel the descriptor is an indexed element of the argument block, and a scalar
+    // load inside the k-loop waits, with lgkmcnt, for every LDS read in flight)
+    const unsigned lda2 = __builtin_amdgcn_readfirstlane(p.lda * 2), ldb2 = __builtin_amdgcn_readfirstlane(p.ldb * 2);
+    const char* gp[PPW];
+    int prow[PPW];
+    int kt = 0;                                   // next k-tile to fetch
+    auto plan = [&](const int m0, const int n0, const int k0) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) {
+            const int g = wave + NW * i;
+            const bool isA = i < APW;
+            const int gg = isA ? g : g - 2 * PA;
+            const int PO = isA ? PA : PB;
+            const bool lo = gg >= PO;
+            const int q = lo ? gg - PO : gg;
+            const __half* plane = static_cast<const __half*>(isA ? (lo ? p.A_lo : p.A_hi) : (lo ? p.B_lo : p.B_hi));
+            const int ld = isA ? p.lda : p.ldb, r0 = isA ? m0 : n0, R = isA ? p.M : p.N;
+            const bool km = isA ? AKM : BKM;
+            if (!km) {
+                const int pr = lane >> 2;
+                const int jsrc = (lane & 3) ^ ((4 - (pr >> 2)) & 3);
+                const int row = min(r0 + q * 16 + pr, R - 1);
+                gp[i] = reinterpret_cast<const char*>(plane + (size_t)row * ld + (size_t)k0 * TBK) + jsrc * 16;
+                prow[i] = 0;
+            } else {
+                const int NPH = (isA ? BM : BN) / 32;                    // pieces per half jj of the plane image
+                const int jj = q / NPH, dp = q - jj * NPH;               // piece q = subtiles (jj, dt = 2 dp), (jj, 2 dp + 1)
+                const int col = min(r0 + dp * 32 + km16_piece_col_bytes(0, lane) / 2, R - 8);      // R % 8 == 0 (host): the last whole chunk
+                gp[i] = reinterpret_cast<const char*>(plane + col);
+                prow[i] = km16_piece_row(jj << 1, lane);                 // k-row inside the k-tile, 0 .. 31
+            }
+        }
+        kt = k0;
+    };
+    auto dma_piece = [&](const int i, char* dst) __attribute__((always_inline)) {
+        const bool km = (i < APW) ? AKM : BKM;
+        if (!km) g16_dma_piece(gp[i], dst + i * (NW * 1024));
+        else {
+            const int kv = (i < APW) ? ka_valid : kb_valid;
+            const int krow = min(kt * TBK + prow[i], kv - 1);
+            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(gp[i] + (size_t)krow * ((i < APW) ? lda2 : ldb2)),
+                                             (__attribute__((address_space(3))) void*)(dst + i * (NW * 1024)), 16, 0, 0);
+        }
+    };
+    auto issue = [&](int buf) __attribute__((always_inline)) {
+        char* dst = smem + buf * STAGE + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) dma_piece(i, dst);
+        ++kt;
+    };
+
+    // ---- fragment addresses (bytes inside a stage)
+    const int l15 = lane & 15;
+    const int ch = ((lane >> 4) ^ ((4 - (l15 >> 2)) & 3)) * 16;
+    const int a_off = (wm * (32 * WM) + l15) * 64 + ch, b_off = 2 * PA * 1024 + (wn * (32 * WN) + l15) * 64 + ch;
+    const unsigned lds0 = (unsigned)(uintptr_t)((__attribute__((address_space(3))) char*)smem);      // LDS byte address of stage 0
+    const unsigned akm0 = lds0 + km16_read_lane_off(lane) + wm * RB * 512, bkm0 = lds0 + 2 * PA * 1024 + km16_read_lane_off(lane) + wn * CB * 512;
+
+    f32x4 acc[RB][CB];
+    // fragments as 4-half halves, [2 f], [2 f + 1] = k 0..3 / 4..7 of the lane's 8.  A sets (one per phase): f = {hi rb 0, hi rb 1, lo rb 0,
+    // lo rb 1} of the phase's two row blocks; B: f = column block (hi), CB + column block (lo)
+    h4 fa0[8], fa1[8], fb[4 * CB];
+    auto tr_off = [](const unsigned addr, auto offc) __attribute__((always_inline)) { return km_tr_read<decltype(offc)::value>(addr); };
+    // RI-th LDS read instruction of the A set of phase PH / of column block J; st = stage pointer, so = its byte offset
+    auto read_a = [&](auto ric, auto phc, const char* st, const unsigned so, h4(&fa)[8]) __attribute__((always_inline)) {
+        constexpr int RI = decltype(ric)::value, PH = decltype(phc)::value;
+        constexpr int f = RI / NDA, half = RI % NDA, pl = f >> 1, rbk = 2 * PH + (f & 1);
+        if constexpr (!AKM) {
+            const h8 v = *reinterpret_cast<const h8*>(st + pl * (PA * 1024) + a_off + rbk * 1024);
+            fa[2 * f] = __builtin_shufflevector(v, v, 0, 1, 2, 3);
+            fa[2 * f + 1] = __builtin_shufflevector(v, v, 4, 5, 6, 7);
+        } else {
+            fa[2 * f + half] = tr_off(akm0 + so, std::integral_constant<int, pl * (PA * 1024) + (half * (BM / 16) + rbk) * 512>{});
+        }
+    };
+    auto read_b = [&](auto ric, auto jc, const char* st, const unsigned so) __attribute__((always_inline)) {
+        constexpr int RI = decltype(ric)::value, J = decltype(jc)::value;
+        constexpr int pl = RI / NDB, half = RI % NDB, f = pl * CB + J;
+        if constexpr (!BKM) {
+            const h8 v = *reinterpret_cast<const h8*>(st + pl * (PB * 1024) + b_off + J * 1024);
+            fb[2 * f] = __builtin_shufflevector(v, v, 0, 1, 2, 3);
+            fb[2 * f + 1] = __builtin_shufflevector(v, v, 4, 5, 6, 7);
+        } else {
+            fb[2 * f + half] = tr_off(bkm0 + so, std::integral_constant<int, pl * (PB * 1024) + (half * (BN / 16) + J) * 512>{});
+        }
+    };
+    auto frag = [](const h4 lo, const h4 hi) __attribute__((always_inline)) { return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7); };
+    // n-th MFMA of column block J in phase PH: its two accumulators, main, then hi x lo, then lo x hi
+    auto mfma_n = [&](auto phc, auto jc, auto nc, const h4(&fa)[8]) __attribute__((always_inline)) {
+        constexpr int PH = decltype(phc)::value, J = decltype(jc)::value, n = decltype(nc)::value, pass = n / 2, k = n % 2;
+        constexpr int af = pass == 2 ? 2 + k : k, bf = pass == 1 ? CB + J : J;
+        acc[2 * PH + k][J] = __builtin_amdgcn_mfma_f32_16x16x32_f16(frag(fa[2 * af], fa[2 * af + 1]), frag(fb[2 * bf], fb[2 * bf + 1]),
+                                                                    acc[2 * PH + k][J], 0, 0, 0);
+    };
+    // A column block = 6 MFMAs with NS load slots spread evenly between them IN THIS ORDER (slot s, then its share of the MFMAs): the
+    // stream is written out and pinned (sched_barrier(0)), since issue-order hints cannot see the inline-asm reads
+    constexpr int NMB = 6;
+    auto block = [&](auto phc, auto jc, auto nsc, const h4(&fa)[8], auto&& slot) __attribute__((always_inline)) {
+        constexpr int NS = decltype(nsc)::value;
+        if constexpr (NS == 0) {
+            static_for<NMB>([&](auto nc) __attribute__((always_inline)) { mfma_n(phc, jc, nc, fa); });
+        } else {
+            static_for<NS>([&](auto sc) __attribute__((always_inline)) {
+                constexpr int S = decltype(sc)::value, n0 = S * NMB / NS, n1 = (S + 1) * NMB / NS;
+                slot(sc);
+                static_for<n1 - n0>([&](auto kc) __attribute__((always_inline)) { mfma_n(phc, jc, std::integral_constant<int, n0 + decltype(kc)::value>{}, fa); });
+                __builtin_amdgcn_sched_barrier(0);
+            });
+        }
+    };
+    // waits for inline-asm reads: lgkmcnt(0) with the released fragments as in / out operands (an MFMA is no memory operation)
+    auto wait_a = [](h4(&f)[8]) __attribute__((always_inline)) {
+        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(f[0]), "+v"(f[1]), "+v"(f[2]), "+v"(f[3]), "+v"(f[4]), "+v"(f[5]), "+v"(f[6]), "+v"(f[7]) : : "memory");
+    };
+    auto pin4 = [](h4& a, h4& b, h4& c, h4& d) __attribute__((always_inline)) { asm volatile("" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : : "memory"); };
+    auto pin_b = [&](auto jc) __attribute__((always_inline)) {      // (behind a wait: carries column block J's four halves)
+        constexpr int J = decltype(jc)::value;
+        pin4(fb[2 * J], fb[2 * J + 1], fb[2 * (CB + J)], fb[2 * (CB + J) + 1]);
+    };
+    constexpr std::integral_constant<int, 0> P0{};
+    constexpr std::integral_constant<int, 1> P1{};
+    constexpr std::integral_constant<int, CB - 1> JL{};
+    // One k-tile in stage rb.  On entry the reads of A(phase 0) and of B column blocks 0 .. CB - 2 are in flight.  LOAD: tile t + 1 (stage
+    // nb) follows; DMA: tile t + STAGES is fetched into stage rb; VM: the vmcnt of the mid-tile wait.
+    auto k_tile = [&](auto loadc, auto dmac, auto vmc, const int rb, const int nb) __attribute__((always_inline)) {
+        constexpr bool LOAD = decltype(loadc)::value, DMA = decltype(dmac)::value;
+        const char* st = smem + rb * STAGE;
+        const char* nx = smem + nb * STAGE;
+        const unsigned so = (unsigned)(rb * STAGE), son = (unsigned)(nb * STAGE);
+        wait_a(fa0);
+        static_for<CB - 1>([&](auto jc) __attribute__((always_inline)) { pin_b(jc); });
+        __builtin_amdgcn_sched_barrier(0);
+        // phase 0: the last B column block, then A(phase 1), under the first CB - 1 column blocks
+        constexpr int NL0 = NLB + NLA;
+        static_for<CB - 1>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int J = decltype(jc)::value, L0 = J * NL0 / (CB - 1), L1 = (J + 1) * NL0 / (CB - 1);
+            block(P0, jc, std::integral_constant<int, L1 - L0>{}, fa0, [&](auto sc) __attribute__((always_inline)) {
+                constexpr int L = L0 + decltype(sc)::value;
+                if constexpr (L < NLB) read_b(std::integral_constant<int, L>{}, JL, st, so);
+                else read_a(std::integral_constant<int, L - NLB>{}, P1, st, so, fa1);
+            });
+        });
+        wait_a(fa1);
+        pin_b(JL);
+        __builtin_amdgcn_sched_barrier(0);
+        block(P0, JL, std::integral_constant<int, 0>{}, fa0, [](auto) {});
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (LOAD) {
+            // every read of stage rb has returned (above); my pieces of tile t + 1 landed; everyone's, and everyone done with stage rb
+            __builtin_amdgcn_s_waitcnt(WAIT_LGKM0_VM(decltype(vmc)::value));
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+        }
+        // phase 1
+        char* dst = smem + rb * STAGE + wave * 1024;
+        static_for<CB>([&](auto jc) __attribute__((always_inline)) {
+            constexpr int J = decltype(jc)::value;
+            constexpr int D0 = DMA ? J * PPW / CB : 0, D1 = DMA ? (J + 1) * PPW / CB : 0;      // this block's DMA pieces
+            constexpr int NRD = LOAD ? (J == 0 ? NLA : NLB) : 0;
+            block(P1, jc, std::integral_constant<int, NRD + (D1 - D0)>{}, fa1, [&](auto sc) __attribute__((always_inline)) {
+                constexpr int S = decltype(sc)::value;
+                if constexpr (S < NRD) {
+                    if constexpr (J == 0) read_a(sc, P0, nx, son, fa0);
+                    else read_b(sc, std::integral_constant<int, J - 1>{}, nx, son);
+                } else {
+                    constexpr int I = D0 + S - NRD;
+                    dma_piece(I, dst);
+                    if constexpr (I == PPW - 1) ++kt;
+                }
+            });
+        });
+        __builtin_amdgcn_sched_barrier(0);
+    };
+
+    int bid = bid0;
+    int pos = 0, pend = 0;
+    int m0, n0;
+    if constexpr (SK) {
+        const int T = order.nblk * ntf, G = grid;
+        if (p.sk_slices > 0) {
+            // aligned k-slices: see gemm_f16x3_km_body
+            const int S = p.sk_slices, nblk = order.nblk, U = nblk * S;
+            const int xcd = bid & 7, idx = bid >> 3;
+            const int ulo = (int)((long)U * xcd / 8), uhi = (int)((long)U * (xcd + 1) / 8);
+            if (idx >= uhi - ulo) return;
+            const int u = ulo + idx;
+            const int slice = u / nblk, lid = u - slice * nblk;
+            const int per = (ntf + S - 1) / S;
+            const int k0 = slice * per;
+            nt = min(per, ntf - k0);            // >= 3 for every slice (host)
+            pos = lid * ntf + k0;
+            pend = pos + nt;
+            order.lid_origin(lid, m0, n0);
+            plan(m0, n0, k0);
+        } else {
+            const int L = (bid & 7) * (G >> 3) + (bid >> 3);
+            auto cut = [&](const int l) {
+                int x = (int)((long)T * l / G);
+                const int r = x % ntf;
+                if (r && r < 3) x -= r;
+                else if (r > ntf - 3) x += ntf - r;
+                return x;
+            };
+            pos = cut(L);
+            pend = cut(L + 1);
+            if (pos >= pend) return;
+            const int lid = pos / ntf, k0 = pos - lid * ntf;
+            nt = min(pend - pos, ntf - k0);
+            order.lid_origin(lid, m0, n0);
+            plan(m0, n0, k0);
+        }
+    } else if constexpr (ONESHOT) {
+        if (bid >= order.nblk) return;       // grouped launch: bid0 IS the tile's position in this problem's grouped order
+        order.lid_origin(bid, m0, n0);
+        plan(m0, n0, 0);
+    } else {
+        if (!order.has_tile(bid)) return;
+        order.tile_origin(bid, m0, n0);
+        plan(m0, n0, 0);
+    }
+#pragma unroll
+    for (int s = 0; s < STAGES; ++s) issue(s);
+    bool first = true;
+    float amx = 0.f;
+    for (;;) {
+#pragma unroll
+        for (int i = 0; i < RB; ++i)
+#pragma unroll
+            for (int j = 0; j < CB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((STAGES - 1) * PPW) : "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        first = false;
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        static_for<NLA>([&](auto rc) __attribute__((always_inline)) { read_a(rc, P0, smem, 0u, fa0); });
+        static_for<CB - 1>([&](auto jc) __attribute__((always_inline)) {
+            static_for<NLB>([&](auto rc) __attribute__((always_inline)) { read_b(rc, jc, smem, 0u); });
+        });
+        __builtin_amdgcn_sched_barrier(0);
+        int rb = 0;
+        int t = 0;
+        for (; t + STAGES < nt; ++t) {
+            const int nb = rb + 1 == STAGES ? 0 : rb + 1;
+            k_tile(std::true_type{}, std::true_type{}, std::integral_constant<int, (STAGES - 2) * PPW>{}, rb, nb);
+            rb = nb;
+        }
+        for (; t + 1 < nt; ++t) {
+            const int nb = rb + 1 == STAGES ? 0 : rb + 1;
+            k_tile(std::true_type{}, std::false_type{}, std::integral_constant<int, 0>{}, rb, nb);
+            rb = nb;
+        }
+        k_tile(std::false_type{}, std::false_type{}, std::integral_constant<int, 0>{}, rb, rb);
+        // every wave has left the k-loop -> the stages are free: start the next tile's pipeline, then write this tile out
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        const int mw = m0 + wm * (32 * WM), nw = n0 + wn * (32 * WN);
+        bool more;
+        if constexpr (SK) {
+            pos += nt;
+            more = pos < pend;
+            if (more) {
+                nt = min(pend - pos, ntf);
+                order.lid_origin(pos / ntf, m0, n0);
+                plan(m0, n0, 0);
+            }
+        } else if constexpr (ONESHOT) {
+            more = false;                 // one tile per block (grouped launch)
+        } else {
+            bid += grid;
+            more = order.has_tile(bid);
+            if (more) {
+                order.tile_origin(bid, m0, n0);
+                plan(m0, n0, 0);
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int s = 0; s < STAGES; ++s) issue(s);
+        }
+        gemm16_epilogue_side16<ACC != 0, ACC == 1, ONESHOT>(p, acc, reinterpret_cast<float*>(smem + STAGES * STAGE) + wave * 512, mw, nw, lane, amx);
+        if (!more) break;
+    }
+    if (p.amax_out)
+        gemm16_amax_flush(static_cast<unsigned int*>(p.amax_out), amx, reinterpret_cast<float*>(smem + STAGES * STAGE), wave, lane,
+                          NWM * NWN);
+}
+
+// MF: the MFMA shape of the body, 32 (32x32x16, gemm_f16x3_km_body) or 16 (16x16x32, gemm_f16x3_km16_body)
+template <int WM, int WN, int NWM, int NWN, int WPS, bool SK, int ACC, bool AKM, bool BKM, int STAGES = 3, int MF = 32>
 __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_km_kernel(const dupl_gemm16_desc p, const int g_gm) {
-    gemm_f16x3_km_body<WM, WN, NWM, NWN, WPS, SK, ACC, AKM, BKM, STAGES>(p, g_gm, blockIdx.x, gridDim.x);
+    static_assert(MF == 16 || MF == 32, "MFMA shape");
+    if constexpr (MF == 16) gemm_f16x3_km16_body<WM, WN, NWM, NWN, WPS, SK, ACC, AKM, BKM, STAGES>(p, g_gm, blockIdx.x, gridDim.x);
+    else gemm_f16x3_km_body<WM, WN, NWM, NWN, WPS, SK, ACC, AKM, BKM, STAGES>(p, g_gm, blockIdx.x, gridDim.x);
 }
 
 // Grouped weight gradients (round 4): the four dW of one transformer block -- 2304 x 768, 768 x 768, 3072 x 768, 768 x 3072, each
@@ -1740,7 +2142,7 @@ struct g16_group_args {
     int first[DUPL_GEMM16_GROUP_MAX + 1];
     int n;
 };
-template <int WM, int WN, int NWM, int NWN, int WPS>
+template <int WM, int WN, int NWM, int NWN, int WPS, int MF = 32>
 __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_km_group_kernel(const g16_group_args g, const int g_gm) {
     // tile list = problem after problem, each in its grouped order (g_gm row tiles x all column tiles per group); XCD x (= blockIdx % 8)
     // takes the x-th eighth of the LIST: ~27 consecutive tiles of (mostly) one problem = 4-5 row tiles x all its column tiles, whose dy
@@ -1756,7 +2158,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_km_group_kerne
     while (i + 1 < g.n && t >= g.first[i + 1]) ++i;
     i = __builtin_amdgcn_readfirstlane(i);
     // one tile per block: a step of the whole grid ends the persistent walk after the first tile
-    gemm_f16x3_km_body<WM, WN, NWM, NWN, WPS, false, 2, true, true, 3, true>(g.d[i], g_gm, t - g.first[i], 1 << 28);
+    if constexpr (MF == 16) gemm_f16x3_km16_body<WM, WN, NWM, NWN, WPS, false, 2, true, true, 3, true>(g.d[i], g_gm, t - g.first[i], 1 << 28);
+    else gemm_f16x3_km_body<WM, WN, NWM, NWN, WPS, false, 2, true, true, 3, true>(g.d[i], g_gm, t - g.first[i], 1 << 28);
 }
 
 }  // namespace
@@ -1767,6 +2170,16 @@ constexpr int G16_GROUP_M = 8;      // 128-row tile kernels
 constexpr int G16_GROUP_RING = 2;   // row tiles (256 rows) per group of the ring kernels' block order: 512-row A bands stay in an
                                     // XCD's L2 while it sweeps the columns (2 / 3: 320, 4: 312, 8: 304, 16: 285 TF/s-eq on 15696 x 3072 x 768)
 constexpr int G16_F1_BIG_FROM = 96; // format 1: 256 x 256 tiles from this many of them
+
+// The k-major launches' automatic choice of the body (dupl_gemm16_desc.tile 0): per instantiation, the 16x16x32 body only where the
+// stand-alone A/B on the step's own shapes shows it faster (profiles/kmajor16_bodies.txt).  The whole-tile weight gradients (single
+// launch in deterministic mode, grouped launch) switch together: they carry the same bits.
+// (us per launch, median of 5 interleaved rounds, one stream / next to the same launch on a second stream; 32x32x16 -> 16x16x32)
+constexpr bool KM16_DGRAD_EPI = true;       // data gradient, full epilogue: 3140 x 3072 x 768 dgelu + amax 74.8 -> 72.4 / 117.2 -> 106.6; 3140 x 768 x 768 amax 31.8 -> 31.3 / 32.9 -> 32.9
+constexpr bool KM16_DGRAD_SK = true;        // stream-K data gradient: 3140 x 768 x 3072 60.2 -> 56.6 / 102.4 -> 93.1; 3140 x 768 x 2304 51.2 -> 48.5 / 82.4 -> 76.4
+constexpr bool KM16_WGRAD_SK = false;       // stream-K weight gradient: not in the step, not measured -- stays on the 32x32x16 body
+constexpr bool KM16_WGRAD_TILE = true;      // whole-tile weight gradients: a block's four at K = 3168, grouped, 121.7 -> 112.5 / 239.8 -> 224.9
+static bool g16_km16(const int tile, const bool automatic) { return tile == 26 || (tile != 24 && automatic); }
 
 extern "C" int dupl_split_f16x2(const float* x, void* hi, void* lo, int64_t n, dupl_stream_t stream) {
     if (!x || !hi || !lo || n <= 0 || (n & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(hi) & 7) ||
@@ -1815,7 +2228,7 @@ extern "C" int dupl_gemm_f16x3_group(const dupl_gemm16_desc* descs, int32_t n, d
     if (!descs || n < 1 || n > DUPL_GEMM16_GROUP_MAX) return DUPL_ERR_ARG;
     g16_group_args g;
     g.n = n;
-    int total = 0, group = 0;
+    int total = 0, group = 0, tile = 0;
     for (int i = 0; i < n; ++i) {
         const dupl_gemm16_desc& d = descs[i];
         if (!g16_operands_ok(d)) return DUPL_ERR_ARG;
@@ -1828,10 +2241,14 @@ extern "C" int dupl_gemm_f16x3_group(const dupl_gemm16_desc* descs, int32_t n, d
         const int nblk = ((d.M + 255) / 256) * ((d.N + 127) / 128);
         total += nblk;                          // first[] counts TILES: the kernel deals the list to the XCDs in eighths
         if (d.group) group = d.group;
+        if (d.tile) tile = d.tile;              // (24 / 26 choose the body; every other code is the library's choice)
     }
     g.first[n] = total;
-    DUPL_LAUNCH((gemm_f16x3_km_group_kernel<2, 2, 4, 2, 2>), dim3((unsigned)(8 * ((total + 7) / 8))), dim3(512), 0, (hipStream_t)stream, g,
-                       group ? group : G16_GROUP_RING);
+    const dim3 grid((unsigned)(8 * ((total + 7) / 8)));
+    if (g16_km16(tile, KM16_WGRAD_TILE))
+        DUPL_LAUNCH((gemm_f16x3_km_group_kernel<2, 2, 4, 2, 2, 16>), grid, dim3(512), 0, (hipStream_t)stream, g, group ? group : G16_GROUP_RING);
+    else
+        DUPL_LAUNCH((gemm_f16x3_km_group_kernel<2, 2, 4, 2, 2, 32>), grid, dim3(512), 0, (hipStream_t)stream, g, group ? group : G16_GROUP_RING);
     return dupl_launch_status();
 }
 
@@ -1869,6 +2286,8 @@ constexpr int G16_TILES[] = {
     14,   // gemm_f16x3_pring_kernel SINGLE, 256 x 128; format 1, persistent
     18,   // gemm_f16x3_ring16_kernel, 256 x 256; format 1 on the 16x16x32 MFMA, one block per tile
     22,   // gemm_f16x3_ring16_kernel, 256 x 128; format 1 on the 16x16x32 MFMA, one block per tile
+    24,   // k-major launches (single and grouped): gemm_f16x3_km_body, the 32x32x16 MFMA; any other launch: as 0
+    26,   // k-major launches (single and grouped): gemm_f16x3_km16_body, the 16x16x32 MFMA; any other launch: as 0
 };
 
 // The two forward tiles on the 16x16x32 MFMA (gemm_f16x3_ring16_kernel), for the format 1 f16x3 forward and the single-product forward
@@ -1920,7 +2339,9 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
     bool known_tile = false;
     for (const int t : G16_TILES) known_tile |= d->tile == t;
     if (!known_tile) return DUPL_ERR_ARG;
-    const int g16_tile = d->tile, g16_concurrency = d->concurrency > 0 ? d->concurrency : 1;
+    const bool kmajor = d->a_layout || d->b_layout;
+    const int g16_tile = (d->tile == 24 || d->tile == 26) && !kmajor ? 0 : d->tile;      // (the k-major bodies' codes mean nothing elsewhere)
+    const int g16_concurrency = d->concurrency > 0 ? d->concurrency : 1;
     const int g16_persist_blocks = d->persist_blocks ? d->persist_blocks : (g16_concurrency >= 2 ? 192 : 256);
     const int g16_group_m = d->group ? d->group : G16_GROUP_M, g16_group_ring = d->group ? d->group : G16_GROUP_RING;
     if (!d->C && !d->C_hi) return DUPL_ERR_ARG;
@@ -1933,7 +2354,6 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
     if (accum && (!d->C || d->C_hi || d->bias || d->res || d->c_rows)) return DUPL_ERR_ARG;   // C += alpha * A B^T, nothing else
     if (d->c_rows < 0 || (d->c_rows && (d->flags & (DUPL_GEMM_MUL_DGELU | DUPL_GEMM_MUL_RELUMASK)))) return DUPL_ERR_ARG;
     if (d->amax_out && (accum || d->c_rows || (reinterpret_cast<uintptr_t>(d->amax_out) & 3))) return DUPL_ERR_ARG;
-    const bool kmajor = d->a_layout || d->b_layout;
     if (d->fmt < 0 || d->fmt > 1 || d->out_exp < 0 || d->out_exp > 15 || (d->out_exp && d->fmt != 1) ||
         (d->fmt == 1 && !kmajor && (accum || d->amax_out)))
         return DUPL_ERR_ARG;
@@ -2011,14 +2431,27 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
             // a data gradient with a LINEAR epilogue (dx = alpha dy . W, nothing else) into a zero-filled dx: stream-K pieces meet in
             // fp32 atomics, so that the N = 768 outputs (78 tiles of 256 x 128 at 4 images, 42 at 2) run on every CU
             if (!d->b_layout || d->deterministic) return DUPL_ERR_ARG;      // (the caller takes the one-block-per-tile form then)
-            DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, false, true>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
+            if (g16_km16(g16_tile, KM16_DGRAD_SK))
+                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, false, true, 3, 16>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
+            else
+                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, false, true, 3, 32>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
         } else if (accum) {
             if (!(d->a_layout && d->b_layout)) return DUPL_ERR_ARG;            // the weight gradient: both operands token-major
-            if (sk) DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, true, true>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
-            else DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 2, true, true>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
+            if (sk) {
+                if (g16_km16(g16_tile, KM16_WGRAD_SK))
+                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, true, true, 3, 16>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
+                else
+                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, true, true, 3, 32>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
+            } else if (g16_km16(g16_tile, KM16_WGRAD_TILE))
+                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 2, true, true, 3, 16>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
+            else
+                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 2, true, true, 3, 32>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
         } else {
             if (d->a_layout || !d->b_layout) return DUPL_ERR_ARG;              // the data gradient: dy k-contiguous, W k-major
-            DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
+            if (g16_km16(g16_tile, KM16_DGRAD_EPI))
+                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 16>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
+            else
+                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 32>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
         }
         return dupl_launch_status();
     }

@@ -426,7 +426,8 @@ def wgrad16_group(items, tuning: Optional[dict] = None, fresh=None):
         d.fmt, d.post_scale = 1, 2.0 ** -(getattr(dy16, "exp", 0) + getattr(x16, "exp", 0))
         d.a_layout, d.b_layout = 1, 1
         d.ka_valid, d.kb_valid = Kp, min(x16.rows, Kp)
-        d.group = (tuning if tuning is not None else GEMM16_TUNING)["group"]
+        tn = tuning if tuning is not None else GEMM16_TUNING
+        d.group, d.tile = tn["group"], tn["tile"]      # (tile: 24 / 26 choose the kernel body, anything else is the library's choice)
         descs.append(d)
     for i in range(0, len(descs), _lib.GEMM16_GROUP_MAX):
         chunk = descs[i:i + _lib.GEMM16_GROUP_MAX]

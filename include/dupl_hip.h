@@ -129,7 +129,11 @@ typedef struct dupl_gemm16_desc {
                                              DUPL_GEMM_ACCUM.  Format 1 (one accumulator set): 8: 256x256 on 8 waves, 12: 256x128, 14:
                                              persistent 256x128 -- all on v_mfma_f32_32x32x16_f16; 18: 256x256 and 22: 256x128 on
                                              v_mfma_f32_16x16x32_f16 (what 0 picks for k-contiguous operands; 18 and 22 are bit-identical
-                                             to each other, and differ from 8 / 12 in the last bits: 32 products per MFMA instead of 16) */
+                                             to each other, and differ from 8 / 12 in the last bits: 32 products per MFMA instead of 16).
+                                             k-major operands (also in dupl_gemm_f16x3_group, where the last non-zero code of the group
+                                             holds): 24: the 256x128 persistent kernels on v_mfma_f32_32x32x16_f16, 26: the same kernels on
+                                             v_mfma_f32_16x16x32_f16 (differ in the last bits, as above); every other code, and 24 / 26
+                                             on k-contiguous operands, is the library's choice */
     int32_t concurrency;                  /* how many streams issue split GEMMs at the same time (2 while the two students of
                                              siamese_network run on their own streams, model_dupl.py:157-213): tile heuristic input */
     int32_t persist_blocks;               /* blocks of the persistent kernels, a multiple of 8 (0: 256 alone, 192 at concurrency 2) */

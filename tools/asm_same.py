@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Compare the kernels of two device assembly files (hipcc ... --cuda-device-only -S), symbol by symbol:
     tools/asm_same.py [--map OLD=NEW]... parent.s new.s
-A kernel is SAME when the text between its label and its .Lfunc_end label and its .amdhsa_kernel block are identical.
+A kernel is SAME when the text between its label and its .Lfunc_end label and its .amdhsa_kernel block are identical.  Block labels, and
+the comments that name them, carry the function's ordinal in the file (BB<fn>_<n>), which moves when a kernel is added in front of
+it: the ordinal is dropped before the comparison, and with it the padding in front of a label's comment.
 --map (repeatable) renames on the parent side before the comparison: every occurrence of OLD, a substring of a symbol, becomes NEW."""
 import re
 import sys
@@ -15,6 +17,7 @@ def kernels(path, maps=()):
     for m in re.finditer(r"^\s*\.amdhsa_kernel (\S+)\n(.*?)^\s*\.end_amdhsa_kernel", s, re.M | re.S):
         name, hsa = m.group(1), m.group(2)
         body = re.search(r"^%s:[^\n]*\n(.*?)^\.Lfunc_end\d+:" % re.escape(name), s, re.M | re.S).group(1)
+        body = re.sub(r"[ \t]+;", " ;", re.sub(r"BB\d+_(\d+)", r"BB_\1", body))
         num = {k: int(re.search(r"\.amdhsa_%s (\d+)" % k, hsa).group(1))
                for k in ("next_free_vgpr", "next_free_sgpr", "private_segment_fixed_size", "group_segment_fixed_size")}
         out[name] = (body, hsa, num)

@@ -6,10 +6,14 @@
 //
 // build:  hipcc -O2 --offload-arch=gfx950 -Iinclude tools/gemm16_bench.cpp -Ldupl_amd -ldupl_hip -Wl,-rpath,'$ORIGIN/../dupl_amd' -o tools/gemm16_bench
 // usage:  tools/gemm16_bench [-t 5,6,7] [-n iters] [-s fwd|bwd|all|MxNxK[,MxNxK...]] [-e epilogue] [-c] [-2] [-r rounds]
-//         -e: 0 fp32 out (default), 1 planes out, 2 bias+gelu+store_pre -> planes, 3 bias+res fp32, 4 accumulate (split-K)
+//         -e: 0 fp32 out (default), 1 planes out, 2 bias+gelu+store_pre -> planes, 3 bias+res fp32, 4 accumulate (split-K),
+//             5 fp32 out * gelu'(aux) with the producer amax, 6 fp32 out with the producer amax (the data gradients' epilogues, k-major
+//             operands only; 5 has no counterpart in the reference kernel: its error column is not a check)
 //         -c: correctness only      -2: run every launch on two streams concurrently (the step's two students)
 //         -r: A/B mode -- the variants take turns, `rounds` times each (one process, one device); per variant the median and the minimum
 //             time per launch and the median shader clock of its timed regions (with -f: tiles 8 / 12 against 18 / 22)
+//         -G: the grouped weight gradients of one transformer block (dupl_gemm_f16x3_group: 2304x768, 768x768, 3072x768, 768x3072 at K = 3168,
+//             written with DUPL_GEMM_C_FRESH) instead of the shapes of -s; -t 24,26 = the two kernel bodies, with -r and -2 as above
 //         Without -r a variant prints `t<tile> <TF/s-eq> <GHz> (<err>)`: the shader clock of the timed region is a column of its own, which
 //         the profiles/* tables made with this tool before it was added do not have.
 #include <hip/hip_runtime.h>
@@ -107,6 +111,99 @@ __global__ __launch_bounds__(512) void mfma_probe(const float* src, float* out, 
 
 struct Shape { int M, N, K; };
 
+// -G: one block's four weight gradients as one grouped launch per stream; per tile id the median / min / max time per launch and the
+// median shader clock over `rounds` interleaved rounds, and the largest difference of a result from the first tile id's
+static int run_group(const std::vector<int>& tiles, int iters, int rounds, bool two, hipStream_t* st, hipEvent_t e0, hipEvent_t e1, long long* d_clk,
+                     float* d_stat) {
+    const Shape pr[4] = {{2304, 768, 3168}, {768, 768, 3168}, {3072, 768, 3168}, {768, 3072, 3168}};
+    const int ns = two ? 2 : 1;
+    float *C[2][4], *Cfirst[4];
+    __half *Ah[2][4], *Bh[2][4];
+    dupl_gemm16_desc d[2][4];
+    for (int s = 0; s < ns; ++s)
+        for (int i = 0; i < 4; ++i) {
+            const long nA = (long)pr[i].K * pr[i].M, nB = (long)pr[i].K * pr[i].N, nC = (long)pr[i].M * pr[i].N;
+            float *A, *B;
+            CK(hipMalloc(&A, nA * 4)); CK(hipMalloc(&B, nB * 4)); CK(hipMalloc(&C[s][i], nC * 4));
+            CK(hipMalloc(&Ah[s][i], nA * 4)); CK(hipMalloc(&Bh[s][i], nB * 4));
+            if (s == 0) CK(hipMalloc(&Cfirst[i], nC * 4));
+            fill_kernel<<<1024, 256>>>(A, nA, 11 + 7 * i + s, 1.0f);
+            fill_kernel<<<1024, 256>>>(B, nB, 23 + 7 * i + s, 0.05f);
+            if (dupl_split_f16x2b(A, Ah[s][i], Ah[s][i] + nA, nA, 3, nullptr) || dupl_split_f16x2b(B, Bh[s][i], Bh[s][i] + nB, nB, 9, nullptr)) return 2;
+            CK(hipDeviceSynchronize());
+            hipFree(A); hipFree(B);
+            dupl_gemm16_desc& q = d[s][i];
+            memset(&q, 0, sizeof q);
+            q.struct_size = sizeof q;
+            q.A_hi = Ah[s][i]; q.A_lo = Ah[s][i] + nA; q.B_hi = Bh[s][i]; q.B_lo = Bh[s][i] + nB;
+            q.M = pr[i].M; q.N = pr[i].N; q.K = pr[i].K; q.lda = q.M; q.ldb = q.N; q.ldc = q.N; q.ldo = q.N;
+            q.a_layout = q.b_layout = 1; q.fmt = 1; q.post_scale = 1.f / 4096.f;
+            q.C = C[s][i]; q.flags = DUPL_GEMM_ACCUM | DUPL_GEMM_C_FRESH;
+            q.concurrency = ns;
+        }
+    std::vector<std::vector<double>> r_us(tiles.size()), r_ghz(tiles.size());
+    std::vector<float> r_diff(tiles.size(), 0.f);
+    auto launch = [&](int s, int tile) {
+        for (int i = 0; i < 4; ++i) d[s][i].tile = tile;
+        return dupl_gemm_f16x3_group(d[s], 4, st[s]);
+    };
+    for (int round = 0; round < (rounds > 0 ? rounds : 1); ++round)
+        for (size_t ti = 0; ti < tiles.size(); ++ti) {
+            const int tile = tiles[ti];
+            if (launch(0, tile)) { printf("  t%d refused\n", tile); return 2; }
+            CK(hipStreamSynchronize(st[0]));
+            if (round == 0)
+                for (int i = 0; i < 4; ++i) {
+                    const long nC = (long)pr[i].M * pr[i].N;
+                    if (ti == 0) { CK(hipMemcpy(Cfirst[i], C[0][i], nC * 4, hipMemcpyDeviceToDevice)); continue; }
+                    CK(hipMemset(d_stat, 0, 8));
+                    maxdiff_kernel<<<1024, 256>>>(C[0][i], Cfirst[i], nC, d_stat);
+                    float hs[2];
+                    CK(hipMemcpy(hs, d_stat, 8, hipMemcpyDeviceToHost));
+                    r_diff[ti] = std::max(r_diff[ti], hs[0] / (hs[1] > 0 ? hs[1] : 1.f));
+                }
+            for (int w = 0; w < iters / 3 + 1; ++w)
+                for (int s = 0; s < ns; ++s) launch(s, tile);
+            CK(hipDeviceSynchronize());
+            long long c0[16], c1[16];
+            clock_probe<<<64, 64, 0, st[0]>>>(d_clk);
+            CK(hipEventRecord(e0, st[0]));
+            if (two) CK(hipStreamWaitEvent(st[1], e0, 0));
+            for (int it = 0; it < iters; ++it)
+                for (int s = 0; s < ns; ++s) launch(s, tile);
+            if (two) {
+                CK(hipEventRecord(e1, st[1]));
+                CK(hipStreamWaitEvent(st[0], e1, 0));
+            }
+            CK(hipEventRecord(e1, st[0]));
+            clock_probe<<<64, 64, 0, st[0]>>>(d_clk + 16);
+            CK(hipDeviceSynchronize());
+            float ms;
+            CK(hipEventElapsedTime(&ms, e0, e1));
+            CK(hipMemcpy(c0, d_clk, 128, hipMemcpyDeviceToHost));
+            CK(hipMemcpy(c1, d_clk + 16, 128, hipMemcpyDeviceToHost));
+            double ghz = 0;
+            int nx = 0;
+            for (int x = 0; x < 8; ++x)
+                if (c0[2 * x + 1] && c1[2 * x + 1] > c0[2 * x + 1]) {
+                    ghz += (double)(c1[2 * x] - c0[2 * x]) / ((double)(c1[2 * x + 1] - c0[2 * x + 1]) * 10.0);
+                    ++nx;
+                }
+            r_us[ti].push_back(ms * 1e3 / iters);
+            r_ghz[ti].push_back(nx ? ghz / nx : 0);
+        }
+    printf("grouped wgrad, one block, K 3168%s (us per launch%s):", two ? ", two streams" : "", two ? " pair" : "");
+    for (size_t ti = 0; ti < tiles.size(); ++ti) {
+        std::sort(r_us[ti].begin(), r_us[ti].end());
+        std::sort(r_ghz[ti].begin(), r_ghz[ti].end());
+        const size_t n = r_us[ti].size();
+        printf("  t%d med %.1f min %.1f max %.1f us %.2f GHz (vs t%d %.1e)", tiles[ti], r_us[ti][n / 2], r_us[ti][0], r_us[ti][n - 1], r_ghz[ti][n / 2],
+               tiles[0], r_diff[ti]);
+    }
+    printf("\n");
+    return 0;
+}
+
 static std::vector<int> parse_ints(const char* s) {
     std::vector<int> v;
     while (*s) {
@@ -120,7 +217,7 @@ static std::vector<int> parse_ints(const char* s) {
 int main(int argc, char** argv) {
     std::vector<int> tiles = {5, 6, 7};
     int iters = 20, epi = 0, probe_iters = 40000, window_ms = 0;
-    bool check_only = false, two = false, dbg = false, probe = false, f1 = false;   // f1: format 1 operand planes (single accumulator)
+    bool check_only = false, two = false, dbg = false, probe = false, f1 = false, grouped = false;   // f1: format 1 operand planes (single accumulator)
     std::string sel = "fwd", layout = "nn";
     int group = 0, sk_slices = 0, rounds = 0;
     for (int i = 1; i < argc; ++i) {
@@ -135,6 +232,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "-g") && i + 1 < argc) group = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-r") && i + 1 < argc) rounds = atoi(argv[++i]);
         else if (!strcmp(argv[i], "-L") && i + 1 < argc) layout = argv[++i];   // nn (default) | nk: B k-major (dgrad) | kk: A and B k-major (wgrad, use -e 4)
+        else if (!strcmp(argv[i], "-G")) grouped = true;
         else if (!strcmp(argv[i], "-p")) probe = true;
         else if (!strcmp(argv[i], "-P") && i + 1 < argc) { probe = true; probe_iters = atoi(argv[++i]); }
         else if (!strcmp(argv[i], "-f")) f1 = true;     // format 1 planes: A * 2^3, B * 2^9, unscaled lo; tiles 8 / 18 (256 x 256), 12 / 22 (256 x 128)
@@ -169,6 +267,9 @@ int main(int argc, char** argv) {
     CK(hipEventCreate(&e1));
     float* d_stat;
     CK(hipMalloc(&d_stat, 8));
+    float* d_amax;
+    CK(hipMalloc(&d_amax, 16));
+    CK(hipMemset(d_amax, 0, 16));
     long long* d_clk;
     CK(hipMalloc(&d_clk, 2 * 128));
     CK(hipMemset(d_clk, 0, 256));
@@ -199,6 +300,7 @@ int main(int argc, char** argv) {
             }
         }
     }
+    if (grouped) return run_group(tiles, iters, rounds, two, st, e0, e1, d_clk, d_stat);
     printf("# dupl_gemm_f16x3 stand-alone: epilogue %d, %d iters%s; TF/s-equivalent = 2MNK/t; peak 833 (2500 / 3 products)\n", epi, iters,
            two ? ", two streams" : "");
     for (const Shape& sh : shapes) {
@@ -241,6 +343,8 @@ int main(int argc, char** argv) {
                 case 2: d.C_hi = Ch[s]; d.C_lo = Ch[s] + nC; d.bias = bias; d.aux = aux[s]; d.flags = DUPL_GEMM_GELU | DUPL_GEMM_STORE_PRE; break;
                 case 3: d.C = C[s]; d.bias = bias; d.res = res[s]; break;
                 case 4: d.C = C[s]; d.flags = DUPL_GEMM_ACCUM; break;
+                case 5: d.C = C[s]; d.aux = res[s]; d.flags = DUPL_GEMM_MUL_DGELU; d.amax_out = d_amax; break;
+                case 6: d.C = C[s]; d.amax_out = d_amax; break;
             }
             if (f1) {
                 d.fmt = 1;

@@ -556,7 +556,9 @@ int dupl_attention_bwd16(const void* qkv_hi, const void* qkv_lo, const float* ou
 /* ------------------------------------------------------------------ per-step strong augmentation
  * utils/imutils.py:305-317 augment_data_strong / utils/randomaug.py RandAugment on the device: planar uint8 images
  * (3,H,W), Pillow's exact 8-bit arithmetic (see csrc/augment.hip).  The op sequence per image is drawn on the host. */
-/* transforms.ToPILImage of a float tensor in [0,1] (imutils.py:306,311): out = (uint8)(x * 255) */
+/* transforms.ToPILImage of a float tensor in [0,1] (imutils.py:306,311): out = (uint8)(x * 255), the float32 product
+ * truncated.  Contract: every x is finite and in [0, 1] (what denormalize_img2 produces); the result for a NaN, a negative
+ * or a value above 1 is unspecified. */
 int dupl_aug_to_u8(const float* x, uint8_t* out, int64_t n, dupl_stream_t s);
 /* mode 0: AutoContrast (randomaug.py:62-63), 1: Equalize (randomaug.py:70-71), in place; hist_scratch 768 uint32, lut_scratch 768 bytes */
 int dupl_aug_lut_op(uint8_t* img, int32_t H, int32_t W, int32_t mode, uint32_t* hist_scratch, uint8_t* lut_scratch,

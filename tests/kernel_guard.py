@@ -9,8 +9,9 @@ import torch
 NAN = float("nan")
 EPS24 = 2.0 ** -24
 PAD = 64                     # floats of slack on either side: keeps the 256-byte alignment of the allocation
+PAD_U8 = 256                 # bytes of slack on either side of a uint8 view; front = PAD_U8 + k puts the view k bytes off alignment
 SENT = {torch.float32: (torch.int32, 0x7FC5A5A5), torch.int32: (torch.int32, -0x5A5A5A5B),
-        torch.int64: (torch.int64, -0x5A5A5A5A5A5A5A5B)}
+        torch.int64: (torch.int64, -0x5A5A5A5A5A5A5A5B), torch.uint8: (torch.uint8, 0xA5)}
 
 
 def rnd(*shape, seed=0, scale=1.0):
@@ -25,8 +26,10 @@ def rndint(lo, hi, *shape, seed=0):
 class Guard:
     """A tensor of `shape` inside a larger device allocation; the slack holds a sentinel (a NaN payload for floats)."""
 
-    def __init__(self, shape, dev, dtype=torch.float32, init=None, front=PAD, back=PAD):
+    def __init__(self, shape, dev, dtype=torch.float32, init=None, front=None, back=None):
         self.n = int(np.prod(shape)) if len(shape) else 1
+        slack = PAD_U8 if dtype == torch.uint8 else PAD     # byte-granular kernels: an off-by-one write lands one byte past the view
+        front, back = slack if front is None else front, slack if back is None else back
         self.front, self.back = front, back
         self.buf = torch.empty(self.n + front + back, dtype=dtype, device=dev)
         self.itype, self.pat = SENT[dtype]

@@ -204,3 +204,30 @@ __device__ __forceinline__ void split_f32(float x, __half& hi, __half& lo) {
     hi = __float2half_rn(x);
     lo = __float2half_rn((x - __half2float(hi)) * DUPL_LO_SCALE);
 }
+// The same two splits on PAIRS, beside gelu_phi2: the scale as one packed multiply (v_pk_mul_f32), hi and lo each as ONE
+// v_cvt_pk_f16_f32 per pair, the residual as a packed subtract.  Every operation is the IEEE operation of the scalar form on the same
+// operands (the clamp and the NaN / Inf select stay per element), so hi and lo are the scalar form's bits, saturation and NaN / Inf
+// behaviour included.  The pin holds the PAIR as materialised fp32 values, for the reason given above split_f32_u.
+typedef _Float16 split_h2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ gelu_f32x2 split2_clamp(const gelu_f32x2 x) {
+    gelu_f32x2 r;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float k = fminf(fmaxf(x[c], -65504.f), 65504.f);
+        r[c] = fabsf(x[c]) <= 3.0e38f ? k : x[c];
+    }
+    asm volatile("" : "+v"(r));
+    return r;
+}
+// format 1: hi = fp16(x * scale), lo = fp16(x * scale - hi)
+__device__ __forceinline__ void split2_f32_u(const gelu_f32x2 x, const float scale, split_h2& hi, split_h2& lo) {
+    const gelu_f32x2 y = split2_clamp(x * gelu_f32x2{scale, scale});
+    hi = __builtin_convertvector(y, split_h2);
+    lo = __builtin_convertvector(y - __builtin_convertvector(hi, gelu_f32x2), split_h2);
+}
+// format 0: hi = fp16(x), lo = fp16((x - hi) * 2048)
+__device__ __forceinline__ void split2_f32(const gelu_f32x2 x, split_h2& hi, split_h2& lo) {
+    const gelu_f32x2 y = split2_clamp(x);
+    hi = __builtin_convertvector(y, split_h2);
+    lo = __builtin_convertvector((y - __builtin_convertvector(hi, gelu_f32x2)) * gelu_f32x2{DUPL_LO_SCALE, DUPL_LO_SCALE}, split_h2);
+}

@@ -34,17 +34,13 @@ __global__ __launch_bounds__(256) void split_kernel(const float* __restrict__ x,
                                                     long n4, float scale) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         const float4 v = reinterpret_cast<const float4*>(x)[i];
-        __half h[4], l[4];
+        split_h2 h[2], l[2];      // the pair form (common.h): the scalar form's bits
         if constexpr (F1) {
-            split_f32_u(v.x * scale, h[0], l[0]);
-            split_f32_u(v.y * scale, h[1], l[1]);
-            split_f32_u(v.z * scale, h[2], l[2]);
-            split_f32_u(v.w * scale, h[3], l[3]);
+            split2_f32_u(gelu_f32x2{v.x, v.y}, scale, h[0], l[0]);
+            split2_f32_u(gelu_f32x2{v.z, v.w}, scale, h[1], l[1]);
         } else {
-            split_f32(v.x, h[0], l[0]);
-            split_f32(v.y, h[1], l[1]);
-            split_f32(v.z, h[2], l[2]);
-            split_f32(v.w, h[3], l[3]);
+            split2_f32(gelu_f32x2{v.x, v.y}, h[0], l[0]);
+            split2_f32(gelu_f32x2{v.z, v.w}, h[1], l[1]);
         }
         reinterpret_cast<uint2*>(hi)[i] = *reinterpret_cast<uint2*>(h);
         reinterpret_cast<uint2*>(lo)[i] = *reinterpret_cast<uint2*>(l);
@@ -122,6 +118,32 @@ __device__ __forceinline__ void gemm16_epilogue(const dupl_gemm16_desc& p, f32x1
 }
 
 
+// Epilogue FORMS.  The walk above tests every descriptor flag again per row and per float4 (a runtime loop of ~1 850 instructions per
+// 16 float4, a quarter of them scalar tests and branches, and -- on the residual path -- a full vmcnt(0) drain in front of every load).
+// The step launches five flag combinations only; each is compiled as a form of its own, chosen by the host launcher from the
+// descriptor (g16_epi_form / g16_epi_form_km), with the walk above as EPI_GENERIC for everything else:
+//     EPI_P   bias -> result planes (format 1 of out_exp, or format 0), no fp32 C                         (qkv)
+//     EPI_G   bias, STORE_PRE for rows < c_rows if asked, GELU -> planes (either format)                  (fc1)
+//     EPI_R   bias + residual -> fp32 C                                                                   (proj, fc2)
+//     EPI_D   alpha . tile . gelu'(aux) -> fp32 C, amax                                                   (k-major data gradient of fc2)
+//     EPI_A   alpha . tile -> fp32 C, amax                                                                (k-major data gradient of proj)
+// A form is the same arithmetic on the same values in the same order: the same bits (tests/test_gemm_epilogue_forms_gpu.py).
+enum : int { EPI_GENERIC = 0, EPI_P = 1, EPI_G = 2, EPI_R = 3, EPI_D = 4, EPI_A = 5 };
+// The epilogues hand a tile from lane to lane through LDS: a lane reads what OTHER lanes of its wave parked.  The hardware runs a wave's
+// LDS instructions in order, but the compiler orders a thread's accesses only where it cannot prove them disjoint -- and in the
+// straight-line code of a form it can (a lane never reads its own floats), and then moves the reads over the writes.  So the forms put
+// this compiler-only fence between the parking and the walk, both ways.  It takes the LDS pointer as an operand: a memory clobber alone
+// does not cover an object whose address the asm cannot know (the kernel's own __shared__ array), and the reads of one pass were
+// found folded into the previous pass's.
+__device__ __forceinline__ void epi_lds_fence(const float* lds) { asm volatile("" ::"v"(lds) : "memory"); }
+// `vec` of the walk, for the forms
+__device__ __forceinline__ bool g16_epi_vec(const dupl_gemm16_desc& p) {
+    auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+    return !(p.N & 3) && !(p.ldc & 3) && !(p.ldo & 3) && !(p.ldr & 3) && !(p.ldaux & 3) && a16(p.C) && a16(p.res) && a16(p.aux) &&
+           a16(p.bias) && !(reinterpret_cast<uintptr_t>(p.C_hi) & 7) && !(reinterpret_cast<uintptr_t>(p.C_lo) & 7);
+}
+
+
 // Epilogue through LDS (ring kernels): the wave parks its (alpha-scaled) tile in its own LDS region [TH][TW] floats and walks it back
 // row-wise, one float4 (4 consecutive columns) per lane -- 64 lanes = 4 rows x 256 contiguous bytes at TW = 64 -- so that every
 // global access of the epilogue (C, planes, aux, res) is a full-width vector access on whole 128-byte lines instead of 2 x 128-byte
@@ -131,21 +153,30 @@ __device__ __forceinline__ void gemm16_epilogue(const dupl_gemm16_desc& p, f32x1
 // columns when r & 4, see gemm16_epilogue_lds16.
 // Vector path needs N, ldc, ldo, ldr, ldaux multiples of 4 and 16-byte (8 for planes) aligned bases: `vec`, block-uniform;
 // otherwise, and in edge columns, the same values go out element-wise.
-template <int TW, int TH, int NPS, bool ROT, class Park>
+// FORM: EPI_GENERIC reads every flag and pointer from the descriptor; a form (EPI_P / EPI_G / EPI_R, matched by the launcher) is the same
+// code with what the form fixes folded at compile time -- the element-safe walk of a form's edge tiles and non-vector launches.
+template <int TW, int TH, int NPS, bool ROT, int FORM = EPI_GENERIC, class Park>
 __device__ __forceinline__ void gemm16_epilogue_rows(const dupl_gemm16_desc& p, Park&& park, float* __restrict__ tile, const int mw0,
                                                      const int nw, const int lane, const int ksplit, float& amx) {
     constexpr int LPR = TW / 4, RPI = 64 / LPR;
+    constexpr bool GEN = FORM == EPI_GENERIC;
     auto at = [](const int r, const int c) { return r * TW + (ROT ? ((c + ((r >> 2) & 1) * 16) & (TW - 1)) : c); };
     const int fl = p.flags;
-    const bool f_pre = fl & DUPL_GEMM_STORE_PRE, f_gelu = fl & DUPL_GEMM_GELU, f_relu = fl & DUPL_GEMM_RELU;
-    const bool f_acc = fl & DUPL_GEMM_ACCUM, f_dgelu = fl & DUPL_GEMM_MUL_DGELU, f_rmask = fl & DUPL_GEMM_MUL_RELUMASK;
+    const bool f_pre = (GEN || FORM == EPI_G) && (fl & DUPL_GEMM_STORE_PRE), f_gelu = GEN ? fl & DUPL_GEMM_GELU : FORM == EPI_G;
+    const bool f_relu = GEN && (fl & DUPL_GEMM_RELU);
+    const bool f_acc = GEN && (fl & DUPL_GEMM_ACCUM), f_dgelu = GEN && (fl & DUPL_GEMM_MUL_DGELU), f_rmask = GEN && (fl & DUPL_GEMM_MUL_RELUMASK);
     const float out_scale = p.out_exp > 0 ? ldexpf(1.f, p.out_exp) : 0.f;      // > 0: the planes go out in format 1
+    // (read at every use, as the generic walk always did: its code stays what it was)
+    auto res_p = [&]() -> const float* { if constexpr (GEN || FORM == EPI_R) return p.res; else return nullptr; };
+    auto C_p = [&]() -> float* { if constexpr (GEN || FORM == EPI_R) return p.C; else return nullptr; };
 #pragma unroll
     for (int ps = 0; ps < NPS; ++ps) {
     const int mw = mw0 + ps * TH;
+    if constexpr (!GEN) epi_lds_fence(tile);
     park(ps);
-    __half* Ch = static_cast<__half*>(p.C_hi);
-    __half* Cl = static_cast<__half*>(p.C_lo);
+    if constexpr (!GEN) epi_lds_fence(tile);
+    __half* Ch = GEN || FORM != EPI_R ? static_cast<__half*>(p.C_hi) : nullptr;
+    __half* Cl = GEN || FORM != EPI_R ? static_cast<__half*>(p.C_lo) : nullptr;
     auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     const bool vec = !(p.N & 3) && !(p.ldc & 3) && !(p.ldo & 3) && !(p.ldr & 3) && !(p.ldaux & 3) && a16(p.C) && a16(p.res) &&
                      a16(p.aux) && a16(p.bias) && !(reinterpret_cast<uintptr_t>(Ch) & 7) && !(reinterpret_cast<uintptr_t>(Cl) & 7);
@@ -189,7 +220,7 @@ __device__ __forceinline__ void gemm16_epilogue_rows(const dupl_gemm16_desc& p, 
             for (int u = 0; u < EPU; ++u) {
                 const int r = r0 + u * RPI, row = mw + r;
                 if (r < TH && row < p.M) {
-                    if (p.res) rq[u] = *reinterpret_cast<const f32x4*>(p.res + (size_t)row * p.ldr + col);
+                    if (res_p()) rq[u] = *reinterpret_cast<const f32x4*>(res_p() + (size_t)row * p.ldr + col);
                     if (need_aux) aq[u] = *reinterpret_cast<const f32x4*>(p.aux + (size_t)row * p.ldaux + col);
                 }
             }
@@ -232,8 +263,8 @@ _Pragma("unroll") for (int c = 0; c < 4; ++c) if (c < nv) a[c] = auxp[c]; }
                 for (int c = 0; c < 4; ++c) v[c] = a[c] > 0.f ? v[c] : 0.f;
             }
         }
-        if (p.res) {
-            const float* rp = p.res + (size_t)row * p.ldr + col;
+        if (res_p()) {
+            const float* rp = res_p() + (size_t)row * p.ldr + col;
             if (fast) {
                 v[0] += rq[u][0]; v[1] += rq[u][1]; v[2] += rq[u][2]; v[3] += rq[u][3];
             } else
@@ -243,8 +274,8 @@ _Pragma("unroll") for (int c = 0; c < 4; ++c) if (c < nv) v[c] += rp[c]; }
 #pragma unroll
         for (int c = 0; c < 4; ++c)
             if (c < nv) amx = fmaxf(amx, fabsf(v[c]));
-        if (p.C && w32) {
-            float* cp = p.C + (size_t)row * p.ldc + col;
+        if (C_p() && w32) {
+            float* cp = C_p() + (size_t)row * p.ldc + col;
             if (fast) *reinterpret_cast<f32x4*>(cp) = f32x4{v[0], v[1], v[2], v[3]};
             else
                 {
@@ -276,6 +307,96 @@ _Pragma("unroll") for (int c = 0; c < 4; ++c)
         }   // rows of the chunk
     }
     }   // passes
+}
+
+// The forms P, G, R of the row walk on a wave tile that lies wholly inside M x N of a `vec` launch (the caller's test; every other wave
+// takes the walk above): straight-line code per 16-row chunk -- no row or column predicates, the bias in registers, the planes split on
+// pairs, and (R) the residual quads of chunk q + 1 requested before the stores of chunk q go out, across the passes, so that every wait
+// is a counted one.  (The loads stand in front of the stores in the source, and may alias them for the compiler: it keeps the order.)
+template <int FORM, int TW, int TH, int NPS, bool ROT, class Park>
+__device__ __forceinline__ void gemm16_epilogue_rows_form(const dupl_gemm16_desc& p, Park&& park, float* tile, const int mw0,
+                                                          const int nw, const int lane) {
+    static_assert(FORM == EPI_P || FORM == EPI_G || FORM == EPI_R, "forms of the row walk");
+    constexpr int LPR = TW / 4, RPI = 64 / LPR, EPU = 4, CH = EPU * RPI, CPP = TH / CH, NCH = NPS * CPP;
+    static_assert(TH % CH == 0, "whole chunks");
+    auto at = [](const int r, const int c) { return r * TW + (ROT ? ((c + ((r >> 2) & 1) * 16) & (TW - 1)) : c); };
+    const int cl = (lane % LPR) * 4, rl = lane / LPR;
+    const int col = nw + cl;
+    f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+    if (p.bias) bv = *reinterpret_cast<const f32x4*>(p.bias + col);
+    auto row_of = [&](const int q, const int u) { return (q / CPP) * TH + (q % CPP) * CH + u * RPI + rl; };      // in the wave tile
+    if constexpr (FORM == EPI_R) {
+        const float* rp = p.res + (size_t)(mw0 + rl) * p.ldr + col;
+        float* cp = p.C + (size_t)(mw0 + rl) * p.ldc + col;
+        f32x4 rq[2][EPU];
+        auto load = [&](auto qc) __attribute__((always_inline)) {
+            constexpr int Q = decltype(qc)::value;
+#pragma unroll
+            for (int u = 0; u < EPU; ++u)
+                rq[Q & 1][u] = *reinterpret_cast<const f32x4*>(rp + (size_t)((Q / CPP) * TH + (Q % CPP) * CH + u * RPI) * p.ldr);
+        };
+        load(std::integral_constant<int, 0>{});
+        static_for<NCH>([&](auto qc) __attribute__((always_inline)) {
+            constexpr int Q = decltype(qc)::value;
+            if constexpr (Q % CPP == 0) {
+                epi_lds_fence(tile);
+                park(Q / CPP);
+                epi_lds_fence(tile);
+            }
+            if constexpr (Q + 1 < NCH) load(std::integral_constant<int, Q + 1>{});
+#pragma unroll
+            for (int u = 0; u < EPU; ++u) {
+                const f32x4 t = *reinterpret_cast<const f32x4*>(tile + at((Q % CPP) * CH + u * RPI + rl, cl));
+                f32x4 v = t + bv;
+                v += rq[Q & 1][u];
+                *reinterpret_cast<f32x4*>(cp + (size_t)((Q / CPP) * TH + (Q % CPP) * CH + u * RPI) * p.ldc) = v;
+            }
+        });
+    } else {
+        const float out_scale = ldexpf(1.f, p.out_exp);
+        __half* hp = static_cast<__half*>(p.C_hi) + (size_t)(mw0 + rl) * p.ldo + col;
+        __half* lp = static_cast<__half*>(p.C_lo) + (size_t)(mw0 + rl) * p.ldo + col;
+        // STORE_PRE: rows of the wave tile below npre keep their pre-activation (c_rows <= 0: all of them)
+        const bool f_pre = FORM == EPI_G && (p.flags & DUPL_GEMM_STORE_PRE);
+        const int npre = !f_pre ? 0 : (p.c_rows <= 0 ? NPS * TH : p.c_rows - mw0);
+        float* ap = f_pre ? p.aux + (size_t)(mw0 + rl) * p.ldaux + col : nullptr;
+        // F1: the planes go out in format 1 (out_exp > 0: fc1 -> fc2) or in format 0 (qkv -> the split attention); one wave-uniform
+        // choice in front of the walk
+        auto walk = [&](auto f1c) __attribute__((always_inline)) {
+            constexpr bool F1 = decltype(f1c)::value;
+            static_for<NCH>([&](auto qc) __attribute__((always_inline)) {
+                constexpr int Q = decltype(qc)::value;
+                if constexpr (Q % CPP == 0) {
+                    epi_lds_fence(tile);
+                    park(Q / CPP);
+                    epi_lds_fence(tile);
+                }
+#pragma unroll
+                for (int u = 0; u < EPU; ++u) {
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(tile + at((Q % CPP) * CH + u * RPI + rl, cl));
+                    const f32x4 v4 = t + bv;
+                    float v[4] = {v4[0], v4[1], v4[2], v4[3]};
+                    if constexpr (FORM == EPI_G) {
+                        if (row_of(Q, u) < npre) *reinterpret_cast<f32x4*>(ap + (size_t)((Q / CPP) * TH + (Q % CPP) * CH + u * RPI) * p.ldaux) = v4;
+                        gelu4(v);
+                    }
+                    split_h2 h[2], l[2];
+                    if constexpr (F1) {
+                        split2_f32_u(gelu_f32x2{v[0], v[1]}, out_scale, h[0], l[0]);
+                        split2_f32_u(gelu_f32x2{v[2], v[3]}, out_scale, h[1], l[1]);
+                    } else {
+                        split2_f32(gelu_f32x2{v[0], v[1]}, h[0], l[0]);
+                        split2_f32(gelu_f32x2{v[2], v[3]}, h[1], l[1]);
+                    }
+                    const size_t o = (size_t)((Q / CPP) * TH + (Q % CPP) * CH + u * RPI) * p.ldo;
+                    *reinterpret_cast<uint2*>(hp + o) = *reinterpret_cast<const uint2*>(h);
+                    *reinterpret_cast<uint2*>(lp + o) = *reinterpret_cast<const uint2*>(l);
+                }
+            });
+        };
+        if (p.out_exp > 0) walk(std::true_type{});
+        else walk(std::false_type{});
+    }
 }
 
 // The row walk for accumulators of the 32x32 MFMA: the tile is main + cross / 2048, [32 WMP][32 WN] floats per pass.
@@ -311,7 +432,8 @@ __device__ __forceinline__ void gemm16_epilogue_lds(const dupl_gemm16_desc& p, f
 // 4 (lane >> 4) + reg; RBP row blocks per pass.  The b32 writes of one register put lanes l and l + 16 four rows apart, which is a
 // multiple of 32 banks at 64-float rows: rows with bit 2 set are stored rotated by 16 floats, so that a half-wave covers 32 banks;
 // the four rows of one b128 read instruction share that bit, their banks are permuted as a whole -- both stay conflict-free.
-template <int RB, int CB, int RBP>
+// EPI: the epilogue form the launcher matched the descriptor to (interior wave tiles of vector launches; the rest walk generically).
+template <int RB, int CB, int RBP, int EPI = EPI_GENERIC>
 __device__ __forceinline__ void gemm16_epilogue_lds16(const dupl_gemm16_desc& p, f32x4 (&acc)[RB][CB], float* __restrict__ tile,
                                                       const int mw0, const int nw, const int lane, const int ksplit, float& amx) {
     constexpr int TW = 16 * CB, TH = 16 * RBP;
@@ -327,7 +449,14 @@ __device__ __forceinline__ void gemm16_epilogue_lds16(const dupl_gemm16_desc& p,
                 for (int e = 0; e < 4; ++e)
                     tile[(i * 16 + 4 * q + e) * TW + ((j * 16 + l15 + (q & 1) * 16) & (TW - 1))] = acc[ps * RBP + i][j][e] * alpha;
     };
-    gemm16_epilogue_rows<TW, TH, RB / RBP, true>(p, park, tile, mw0, nw, lane, ksplit, amx);
+    if constexpr (EPI != EPI_GENERIC) {
+        // one wave-uniform test: the wave tile wholly inside M x N, and the vector path's conditions
+        if (mw0 + 16 * RB <= p.M && nw + TW <= p.N && g16_epi_vec(p)) {
+            gemm16_epilogue_rows_form<EPI, TW, TH, RB / RBP, true>(p, park, tile, mw0, nw, lane);
+            return;
+        }
+    }
+    gemm16_epilogue_rows<TW, TH, RB / RBP, true, EPI>(p, park, tile, mw0, nw, lane, ksplit, amx);
 }
 
 
@@ -338,23 +467,28 @@ struct Epi16 {
     float out_scale;        // > 0: the result planes go out in format 1 (C * out_scale, unscaled lo)
     __half *Ch, *Cl;
 };
+// FORM: EPI_D / EPI_A fix the flags and pointers at compile time (the launcher matched the descriptor), as in gemm16_epilogue_rows
+template <int FORM = EPI_GENERIC>
 __device__ __forceinline__ Epi16 epi16_setup(const dupl_gemm16_desc& p) {
     Epi16 e;
+    constexpr bool GEN = FORM == EPI_GENERIC;
     const int fl = p.flags;
-    e.f_pre = fl & DUPL_GEMM_STORE_PRE; e.f_gelu = fl & DUPL_GEMM_GELU; e.f_relu = fl & DUPL_GEMM_RELU;
-    e.f_dgelu = fl & DUPL_GEMM_MUL_DGELU; e.f_rmask = fl & DUPL_GEMM_MUL_RELUMASK;
-    e.Ch = static_cast<__half*>(p.C_hi);
-    e.Cl = static_cast<__half*>(p.C_lo);
-    e.out_scale = p.out_exp > 0 ? ldexpf(1.f, p.out_exp) : 0.f;
+    e.f_pre = GEN && (fl & DUPL_GEMM_STORE_PRE); e.f_gelu = GEN && (fl & DUPL_GEMM_GELU); e.f_relu = GEN && (fl & DUPL_GEMM_RELU);
+    e.f_dgelu = GEN ? fl & DUPL_GEMM_MUL_DGELU : FORM == EPI_D; e.f_rmask = GEN && (fl & DUPL_GEMM_MUL_RELUMASK);
+    e.Ch = GEN ? static_cast<__half*>(p.C_hi) : nullptr;
+    e.Cl = GEN ? static_cast<__half*>(p.C_lo) : nullptr;
+    e.out_scale = GEN && p.out_exp > 0 ? ldexpf(1.f, p.out_exp) : 0.f;
     auto a16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     e.vec = !(p.N & 3) && !(p.ldc & 3) && !(p.ldo & 3) && !(p.ldr & 3) && !(p.ldaux & 3) && a16(p.C) && a16(p.res) && a16(p.aux) &&
             a16(p.bias) && !(reinterpret_cast<uintptr_t>(e.Ch) & 7) && !(reinterpret_cast<uintptr_t>(e.Cl) & 7);
     return e;
 }
 // pre / pre_kind: the residual (1) / aux (2) quad of this row when the caller has loaded it already (fast lanes only), else kind 0
+template <int FORM = EPI_GENERIC>
 __device__ __forceinline__ void epi16_quad(const dupl_gemm16_desc& p, const Epi16& E, const int row, const int col, const int nv,
                                            const f32x4 t, const float (&bv)[4], float& amx, const f32x4 pre = f32x4{0.f, 0.f, 0.f, 0.f},
                                            const int pre_kind = 0) {
+    auto res_p = [&]() -> const float* { if constexpr (FORM == EPI_GENERIC) return p.res; else return nullptr; };
     const bool fast = E.vec && nv == 4;
     float v[4] = {t[0] + bv[0], t[1] + bv[1], t[2] + bv[2], t[3] + bv[3]};
     float* auxp = p.aux + (size_t)row * p.ldaux + col;
@@ -386,8 +520,8 @@ __device__ __forceinline__ void epi16_quad(const dupl_gemm16_desc& p, const Epi1
             for (int c = 0; c < 4; ++c) v[c] = a[c] > 0.f ? v[c] : 0.f;
         }
     }
-    if (p.res) {
-        const float* rp = p.res + (size_t)row * p.ldr + col;
+    if (res_p()) {
+        const float* rp = res_p() + (size_t)row * p.ldr + col;
         if (fast) {
             const f32x4 q = pre_kind == 1 ? pre : *reinterpret_cast<const f32x4*>(rp);
             v[0] += q[0]; v[1] += q[1]; v[2] += q[2]; v[3] += q[3];
@@ -527,26 +661,81 @@ __device__ __forceinline__ void gemm16_epilogue_side(const dupl_gemm16_desc& p, 
 // one register put the four lane groups two side rows apart at the same 16 columns: side rows 2 g, 2 g + 1 are stored rotated by 16 g
 // floats, so that one write instruction covers the 64 banks once; a row read back (b128, 16 lanes per row; b32, lane = column) is one
 // whole rotated row -- both stay conflict-free.  Everything a row then meets is epi16_quad / the ACC forms of gemm16_epilogue_side.
-template <bool ACC, bool ATOM, bool OVERW>
+// EPI: EPI_D / EPI_A (the full-epilogue data gradients) run wave tiles wholly inside M x N of a vector launch as straight-line code: no
+// flag, row or column tests, the aux quads of pass q + 1 requested before the stores of pass q go out (a counted wait, no drain).
+template <bool ACC, bool ATOM, bool OVERW, int EPI = EPI_GENERIC>
 __device__ __forceinline__ void gemm16_epilogue_side16(const dupl_gemm16_desc& p, f32x4 (&acc)[4][4], float* __restrict__ side, const int mw,
                                                        const int nw, const int lane, float& amx) {
     const int l15 = lane & 15, g = lane >> 4;
     const float alpha = (p.alpha_dev ? *p.alpha_dev : 1.f) * (p.post_scale != 0.f ? p.post_scale : 1.f);
-    const Epi16 E = epi16_setup(p);
+    const Epi16 E = epi16_setup<EPI>(p);
+    auto res_p = [&]() -> const float* { if constexpr (EPI == EPI_GENERIC) return p.res; else return nullptr; };
+    auto bias_p = [&]() -> const float* { if constexpr (EPI == EPI_GENERIC) return p.bias; else return nullptr; };
     const int cl = l15 * 4, rl = g;
     const int col = nw + cl;
     const int nv = min(4, p.N - col);
     float bv[4] = {0.f, 0.f, 0.f, 0.f};
-    if (!ACC && p.bias && nv > 0) {
+    if (!ACC && bias_p() && nv > 0) {
 #pragma unroll
         for (int c = 0; c < 4; ++c)
-            if (c < nv) bv[c] = p.bias[col + c];
+            if (c < nv) bv[c] = bias_p()[col + c];
     }
     const bool want_aux = E.f_dgelu || E.f_rmask;
-    const bool pre_ld = !ACC && E.vec && nv == 4 && ((p.res != nullptr) != want_aux);
-    const float* pre_src = want_aux ? p.aux : p.res;
+    const bool pre_ld = !ACC && E.vec && nv == 4 && ((res_p() != nullptr) != want_aux);
+    const float* pre_src = want_aux ? p.aux : res_p();
     const int pre_ldm = want_aux ? p.ldaux : p.ldr;
     auto tile_row = [](const int i, const int ep, const int s) { return 16 * i + 4 * (s >> 1) + 2 * ep + (s & 1); };   // of side row s
+    if constexpr (!ACC && (EPI == EPI_D || EPI == EPI_A)) {
+        if (mw + 64 <= p.M && nw + 64 <= p.N && E.vec) {
+            // row of (pass q = (i, ep), k) in the wave tile: tile_row(i, ep, rl + 4 k) = tile_row(0, 0, rl) + 16 i + 2 ep + 8 k -- a lane's own
+            // row plus a constant, which is pinned at its pass (16 + 16 row addresses computed up front spill)
+            const float* xp = p.aux + (size_t)(mw + tile_row(0, 0, rl)) * p.ldaux + col;
+            float* cp = p.C + (size_t)(mw + tile_row(0, 0, rl)) * p.ldc + col;
+            auto pass_row = [](const int q) __attribute__((always_inline)) {
+                int r = 16 * (q >> 1) + 2 * (q & 1);
+                asm volatile("" : "+s"(r));
+                return r;
+            };
+            // (one set of aux quads: the next pass's are requested once this pass's are consumed, still in front of its stores -- a
+            // second set spills)
+            f32x4 aq[2];
+            auto load = [&](auto qc) __attribute__((always_inline)) {
+                constexpr int Q = decltype(qc)::value;
+                const int r0 = pass_row(Q);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) aq[k] = *reinterpret_cast<const f32x4*>(xp + (size_t)(r0 + 8 * k) * p.ldaux);
+            };
+            if constexpr (EPI == EPI_D) load(std::integral_constant<int, 0>{});
+            static_for<8>([&](auto qc) __attribute__((always_inline)) {
+                constexpr int Q = decltype(qc)::value, i = Q >> 1, ep = Q & 1;
+                epi_lds_fence(side);
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int de = 0; de < 2; ++de) side[(2 * g + de) * 64 + ((j * 16 + l15 + 16 * g) & 63)] = acc[i][j][2 * ep + de] * alpha;
+                epi_lds_fence(side);
+                f32x4 vv[2];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int s = rl + 4 * k;
+                    const f32x4 t = *reinterpret_cast<const f32x4*>(side + s * 64 + ((cl + 16 * (s >> 1)) & 63));
+                    float v[4] = {t[0] + 0.f, t[1] + 0.f, t[2] + 0.f, t[3] + 0.f};      // (the walk's `+ bias` without one: -0 -> +0)
+                    if constexpr (EPI == EPI_D) {
+                        const float a[4] = {aq[k][0], aq[k][1], aq[k][2], aq[k][3]};
+                        gelu_grad_mul4(v, a);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) amx = fmaxf(amx, fabsf(v[c]));
+                    vv[k] = f32x4{v[0], v[1], v[2], v[3]};
+                }
+                if constexpr (EPI == EPI_D && Q + 1 < 8) load(std::integral_constant<int, Q + 1>{});
+                const int r0 = pass_row(Q);
+#pragma unroll
+                for (int k = 0; k < 2; ++k) *reinterpret_cast<f32x4*>(cp + (size_t)(r0 + 8 * k) * p.ldc) = vv[k];
+            });
+            return;
+        }
+    }
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
@@ -559,10 +748,12 @@ __device__ __forceinline__ void gemm16_epilogue_side16(const dupl_gemm16_desc& p
                     if (row < p.M) pq[k] = *reinterpret_cast<const f32x4*>(pre_src + (size_t)row * pre_ldm + col);
                 }
             }
+            if constexpr (EPI != EPI_GENERIC) epi_lds_fence(side);
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int de = 0; de < 2; ++de) side[(2 * g + de) * 64 + ((j * 16 + l15 + 16 * g) & 63)] = acc[i][j][2 * ep + de] * alpha;
+            if constexpr (EPI != EPI_GENERIC) epi_lds_fence(side);
             if constexpr (ACC) {
                 if (nw + lane < p.N) {
                     const bool fresh = OVERW && (p.flags & DUPL_GEMM_C_FRESH);      // C = 0 + v: see gemm16_epilogue_side
@@ -584,7 +775,7 @@ __device__ __forceinline__ void gemm16_epilogue_side16(const dupl_gemm16_desc& p
                     const int s = rl + 4 * k;
                     const f32x4 t = *reinterpret_cast<const f32x4*>(side + s * 64 + ((cl + 16 * (s >> 1)) & 63));
                     const int row = mw + tile_row(i, ep, s);
-                    if (nv > 0 && row < p.M) epi16_quad(p, E, row, col, nv, t, bv, amx, pq[k], pre_ld ? (want_aux ? 2 : 1) : 0);
+                    if (nv > 0 && row < p.M) epi16_quad<EPI>(p, E, row, col, nv, t, bv, amx, pq[k], pre_ld ? (want_aux ? 2 : 1) : 0);
                 }
             }
         }
@@ -1060,7 +1251,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring_kernel(co
 //     DMA round trip under.  The k-tile stays ONE MFMA k-step (32), so K % 32 == 0 is all a shape needs.
 //   * a phase is 2 NP CB MFMAs with 2 PL fragment reads under its first PL column blocks.
 //   * NP = 1 alone flushes the epilogue's amax (p.amax_out).
-template <int WM, int WN, int NWM, int NWN, int WPS, int STAGES, int NP = 3>
+//   * EPI: the epilogue form (EPI_P / EPI_G / EPI_R, NP = 3; see gemm16_epilogue_rows_form), EPI_GENERIC for every other descriptor.
+template <int WM, int WN, int NWM, int NWN, int WPS, int STAGES, int NP = 3, int EPI = EPI_GENERIC>
 __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(const dupl_gemm16_desc p, const int g_gm) {
     using G = RingGeom<WM, WN, NWM, NWN>;
     static_assert(NP == 1 || NP == 3, "one product or the three of f16x3");
@@ -1249,7 +1441,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_ring16_kernel(
     constexpr int RBP = RB * WTILE <= STAGES * STAGE ? RB : ((RB / 2) * WTILE <= STAGES * STAGE ? RB / 2 : RB / 4);   // row blocks per pass
     static_assert(RBP >= 1 && RBP * WTILE <= STAGES * STAGE, "epilogue tiles must fit the stages");
     float amx = 0.f;
-    gemm16_epilogue_lds16<RB, CB, RBP>(p, acc, reinterpret_cast<float*>(smem) + wave * ((16 * RBP) * (16 * CB)), m0 + wm * (32 * WM),
+    gemm16_epilogue_lds16<RB, CB, RBP, EPI>(p, acc, reinterpret_cast<float*>(smem) + wave * ((16 * RBP) * (16 * CB)), m0 + wm * (32 * WM),
                                        n0 + wn * (32 * WN), lane, 1, amx);
     if constexpr (NP == 1)
         if (p.amax_out) gemm16_amax_flush(static_cast<unsigned int*>(p.amax_out), amx, reinterpret_cast<float*>(smem), wave, lane, NW);
@@ -1811,7 +2003,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
 //     blocks in order and under block j reads A(phase 0) (j = 0) / B column block j - 1 (in place) of tile t + 1, and issues the DMA of
 //     tile t + STAGES into tile t's stage.  The stream is written out and pinned slot by slot as in gemm_f16x3_km_body; every wait for
 //     an inline-asm read carries the fragments it releases (split_frag.h).
-template <int WM, int WN, int NWM, int NWN, int WPS, bool SK, int ACC, bool AKM, bool BKM, int STAGES = 3, bool ONESHOT = false>
+template <int WM, int WN, int NWM, int NWN, int WPS, bool SK, int ACC, bool AKM, bool BKM, int STAGES = 3, bool ONESHOT = false, int EPI = EPI_GENERIC>
 __device__ __forceinline__ void gemm_f16x3_km16_body(const dupl_gemm16_desc& p, const int g_gm, const int bid0, const int grid) {
     using G = RingGeom<WM, WN, NWM, NWN>;
     constexpr int BM = G::BM, BN = G::BN, NW = G::NW, PA = G::PA, PB = G::PB, STAGE = G::STAGE, PPW = G::PPW;
@@ -2115,7 +2307,7 @@ __device__ __forceinline__ void gemm_f16x3_km16_body(const dupl_gemm16_desc& p, 
 #pragma unroll
             for (int s = 0; s < STAGES; ++s) issue(s);
         }
-        gemm16_epilogue_side16<ACC != 0, ACC == 1, ONESHOT>(p, acc, reinterpret_cast<float*>(smem + STAGES * STAGE) + wave * 512, mw, nw, lane, amx);
+        gemm16_epilogue_side16<ACC != 0, ACC == 1, ONESHOT, EPI>(p, acc, reinterpret_cast<float*>(smem + STAGES * STAGE) + wave * 512, mw, nw, lane, amx);
         if (!more) break;
     }
     if (p.amax_out)
@@ -2124,10 +2316,12 @@ __device__ __forceinline__ void gemm_f16x3_km16_body(const dupl_gemm16_desc& p, 
 }
 
 // MF: the MFMA shape of the body, 32 (32x32x16, gemm_f16x3_km_body) or 16 (16x16x32, gemm_f16x3_km16_body)
-template <int WM, int WN, int NWM, int NWN, int WPS, bool SK, int ACC, bool AKM, bool BKM, int STAGES = 3, int MF = 32>
+// EPI: the epilogue form of the 16x16x32 body's full-epilogue launches (EPI_D / EPI_A: gemm16_epilogue_side16)
+template <int WM, int WN, int NWM, int NWN, int WPS, bool SK, int ACC, bool AKM, bool BKM, int STAGES = 3, int MF = 32, int EPI = EPI_GENERIC>
 __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_km_kernel(const dupl_gemm16_desc p, const int g_gm) {
     static_assert(MF == 16 || MF == 32, "MFMA shape");
-    if constexpr (MF == 16) gemm_f16x3_km16_body<WM, WN, NWM, NWN, WPS, SK, ACC, AKM, BKM, STAGES>(p, g_gm, blockIdx.x, gridDim.x);
+    static_assert(EPI == EPI_GENERIC || (MF == 16 && ACC == 0), "forms: the 16x16x32 body's C = ... launches");
+    if constexpr (MF == 16) gemm_f16x3_km16_body<WM, WN, NWM, NWN, WPS, SK, ACC, AKM, BKM, STAGES, false, EPI>(p, g_gm, blockIdx.x, gridDim.x);
     else gemm_f16x3_km_body<WM, WN, NWM, NWN, WPS, SK, ACC, AKM, BKM, STAGES>(p, g_gm, blockIdx.x, gridDim.x);
 }
 
@@ -2179,7 +2373,34 @@ constexpr bool KM16_DGRAD_EPI = true;       // data gradient, full epilogue: 314
 constexpr bool KM16_DGRAD_SK = true;        // stream-K data gradient: 3140 x 768 x 3072 60.2 -> 56.6 / 102.4 -> 93.1; 3140 x 768 x 2304 51.2 -> 48.5 / 82.4 -> 76.4
 constexpr bool KM16_WGRAD_SK = false;       // stream-K weight gradient: not in the step, not measured -- stays on the 32x32x16 body
 constexpr bool KM16_WGRAD_TILE = true;      // whole-tile weight gradients: a block's four at K = 3168, grouped, 121.7 -> 112.5 / 239.8 -> 224.9
-static bool g16_km16(const int tile, const bool automatic) { return tile == 26 || (tile != 24 && automatic); }
+static bool g16_km16(const int tile, const bool automatic) { return tile == 26 || tile == 32 || (tile != 24 && automatic); }
+
+// The epilogue forms (EPI_*): the launcher matches flags, pointers and c_rows of a descriptor against the forms the step launches and takes
+// the specialised instantiation where the stand-alone A/B on the step's own shapes shows it faster or equal (tools/gemm16_bench with
+// tile 18 / 22 / 26 against 28 / 30 / 32, the same bodies with EPI_GENERIC forced; profiles/epilogue_forms.txt).  Everything else, the
+// ablation builds and the forced codes run the generic walk.
+// (us per launch, median of 5 interleaved rounds, one stream / next to the same launch on a second stream; GENERIC -> form)
+constexpr bool EPI_USE_P = true;        // bias -> planes: 15696 x 2304 x 768 189.1 -> 164.9 / 311.9 -> 289.4; 6280 x 2304 x 768 66.0 -> 60.6 / 124.8 -> 114.0
+constexpr bool EPI_USE_G = true;        // bias, pre, GELU -> planes: 15696 x 3072 x 768 241.3 -> 234.7 / 492.7 -> 461.3; 6280 x 3072 x 768 136.2 -> 122.4 / 191.5 -> 179.9
+constexpr bool EPI_USE_R = true;        // bias + residual -> fp32: 15696 x 768 x 3072 211.0 -> 203.1 / 384.0 -> 370.3; 15696 x 768 x 768 65.4 -> 57.2 / 127.6 -> 110.6;
+                                        // on the 256 x 128 tile 6280 x 768 x 3072 92.4 -> 90.8 / 159.3 -> 155.3; 6280 x 768 x 768 31.6 -> 29.1 / 51.3 -> 48.2
+constexpr bool EPI_USE_D = true;        // gelu' + amax: 3140 x 3072 x 768 73.6 -> 61.5 / 110.4 -> 100.3
+constexpr bool EPI_USE_A = true;        // amax: 3140 x 768 x 768 31.4 -> 26.8 / 33.0 -> 29.2
+static int g16_epi_form(const dupl_gemm16_desc& d) {       // the k-contiguous format 1 forward (gemm_f16x3_ring16_kernel, NP = 3)
+    if (G16_ABL) return EPI_GENERIC;
+    if (d.C_hi && !d.C && !d.res) {
+        if (d.flags == 0) return EPI_USE_P ? EPI_P : EPI_GENERIC;
+        if ((d.flags & ~DUPL_GEMM_STORE_PRE) == DUPL_GEMM_GELU) return EPI_USE_G ? EPI_G : EPI_GENERIC;
+    }
+    if (d.C && !d.C_hi && d.res && d.flags == 0 && d.c_rows == 0) return EPI_USE_R ? EPI_R : EPI_GENERIC;
+    return EPI_GENERIC;
+}
+static int g16_epi_form_km(const dupl_gemm16_desc& d) {    // the full-epilogue data gradient on the 16x16x32 body
+    if (G16_ABL || !d.C || d.C_hi || d.res || d.bias || d.c_rows) return EPI_GENERIC;
+    if (d.flags == DUPL_GEMM_MUL_DGELU) return EPI_USE_D ? EPI_D : EPI_GENERIC;
+    if (d.flags == 0) return EPI_USE_A ? EPI_A : EPI_GENERIC;
+    return EPI_GENERIC;
+}
 
 extern "C" int dupl_split_f16x2(const float* x, void* hi, void* lo, int64_t n, dupl_stream_t stream) {
     if (!x || !hi || !lo || n <= 0 || (n & 3) || (reinterpret_cast<uintptr_t>(x) & 15) || (reinterpret_cast<uintptr_t>(hi) & 7) ||
@@ -2288,6 +2509,9 @@ constexpr int G16_TILES[] = {
     22,   // gemm_f16x3_ring16_kernel, 256 x 128; format 1 on the 16x16x32 MFMA, one block per tile
     24,   // k-major launches (single and grouped): gemm_f16x3_km_body, the 32x32x16 MFMA; any other launch: as 0
     26,   // k-major launches (single and grouped): gemm_f16x3_km16_body, the 16x16x32 MFMA; any other launch: as 0
+    28,   // as 18 with the generic epilogue walk forced (EPI_GENERIC): the A/B partner of the epilogue forms
+    30,   // as 22 with the generic epilogue walk forced
+    32,   // as 26 with the generic epilogue walk forced
 };
 
 // The two forward tiles on the 16x16x32 MFMA (gemm_f16x3_ring16_kernel), for the format 1 f16x3 forward and the single-product forward
@@ -2296,9 +2520,15 @@ static int g16_tile16(const dupl_gemm16_desc& d) {
     return ((d.M + 255) / 256) * ((d.N + 255) / 256) >= G16_F1_BIG_FROM ? 18 : 22;
 }
 using g16_kernel_t = void (*)(dupl_gemm16_desc, int);
-static void g16_launch16(const dupl_gemm16_desc& d, const int t, const bool automatic, const int group, hipStream_t s, g16_kernel_t big,
-                         g16_kernel_t small) {
-    auto launch = [&](g16_kernel_t k, const dupl_gemm16_desc& q, const int bn) {
+// big / small: the instantiations of the two tiles by epilogue form ([EPI_GENERIC] .. [EPI_R]; NULL = that form has none); forms: take
+// them (the form is matched per launch: the two parts of a row split may differ)
+constexpr int EPI_FWD_COUNT = 4;        // forms of the forward kernel, generic included: what g16_epi_form may return
+static_assert(EPI_GENERIC == 0 && EPI_P < EPI_FWD_COUNT && EPI_G < EPI_FWD_COUNT && EPI_R < EPI_FWD_COUNT, "the forward form tables are indexed by EPI_*");
+static void g16_launch16(const dupl_gemm16_desc& d, const int t, const bool automatic, const int group, hipStream_t s,
+                         const g16_kernel_t (&big)[EPI_FWD_COUNT], const g16_kernel_t (&small)[EPI_FWD_COUNT], const bool forms) {
+    auto launch = [&](const g16_kernel_t (&ks)[EPI_FWD_COUNT], const dupl_gemm16_desc& q, const int bn) {
+        const int f = forms ? g16_epi_form(q) : EPI_GENERIC;
+        const g16_kernel_t k = ks[f] ? ks[f] : ks[EPI_GENERIC];
         DUPL_LAUNCH(k, dim3((unsigned)(((q.M + 255) / 256) * ((q.N + bn - 1) / bn))), dim3(512), 0, s, q, group);
     };
     if (t == 22) return launch(small, d, 128);
@@ -2340,7 +2570,10 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
     for (const int t : G16_TILES) known_tile |= d->tile == t;
     if (!known_tile) return DUPL_ERR_ARG;
     const bool kmajor = d->a_layout || d->b_layout;
-    const int g16_tile = (d->tile == 24 || d->tile == 26) && !kmajor ? 0 : d->tile;      // (the k-major bodies' codes mean nothing elsewhere)
+    // (the k-major bodies' codes mean nothing elsewhere; 28 / 30 are 18 / 22 with the generic epilogue forced, 32 is 26 with it)
+    const bool epi_forms = d->tile != 28 && d->tile != 30 && d->tile != 32;
+    const int tile_code = d->tile == 28 ? 18 : d->tile == 30 ? 22 : d->tile;
+    const int g16_tile = (tile_code == 24 || tile_code == 26 || tile_code == 32) && !kmajor ? 0 : tile_code;
     const int g16_concurrency = d->concurrency > 0 ? d->concurrency : 1;
     const int g16_persist_blocks = d->persist_blocks ? d->persist_blocks : (g16_concurrency >= 2 ? 192 : 256);
     const int g16_group_m = d->group ? d->group : G16_GROUP_M, g16_group_ring = d->group ? d->group : G16_GROUP_RING;
@@ -2448,8 +2681,15 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
                 DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 2, true, true, 3, 32>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
         } else {
             if (d->a_layout || !d->b_layout) return DUPL_ERR_ARG;              // the data gradient: dy k-contiguous, W k-major
-            if (g16_km16(g16_tile, KM16_DGRAD_EPI))
-                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 16>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
+            if (g16_km16(g16_tile, KM16_DGRAD_EPI)) {
+                const int f = epi_forms ? g16_epi_form_km(*d) : EPI_GENERIC;
+                if (f == EPI_D)
+                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 16, EPI_D>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
+                else if (f == EPI_A)
+                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 16, EPI_A>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
+                else
+                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 16>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
+            }
             else
                 DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 32>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
         }
@@ -2469,8 +2709,13 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         // chip holds under this loop is higher on that shape.  Both tiles switch together: they are bit-identical to each other)
         int t = (g16_tile == 8 || g16_tile == 12 || g16_tile == 14 || g16_tile == 18 || g16_tile == 22) ? g16_tile : g16_tile16(*d);
         if (d->K / TBK < 3 && t == 14) t = 12;
-        if (t == 18 || t == 22)
-            g16_launch16(*d, t, g16_tile == 0, g16_group_ring, s, gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>, gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>);
+        if (t == 18 || t == 22) {
+            static const g16_kernel_t big[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>, gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_P>,
+                                                gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_G>, gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_R>};
+            static const g16_kernel_t small[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>, gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_P>,
+                                                  gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_G>, gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_R>};
+            g16_launch16(*d, t, g16_tile == 0, g16_group_ring, s, big, small, epi_forms);
+        }
         else if (t == 8) DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 4, 2, 2, true>), blocks(256, 256), dim3(512), 0, s, *d, g16_group_ring);
         else if (t == 12) DUPL_LAUNCH((gemm_f16x3_ring_kernel<2, 2, 4, 2, 2, 3, true>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
         else
@@ -2503,7 +2748,9 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
 #define G16H_STAGES 4   // ring depth of both tiles (4 x 32 KB / 4 x 24 KB)
 #endif
 static int g16_launch_hi(const dupl_gemm16_desc& d, const int tile, const int group, hipStream_t s) {
-    const g16_kernel_t small = gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, G16H_STAGES, 1>, big = gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, G16H_STAGES, 1>;
-    g16_launch16(d, (tile == 18 || tile == 22) ? tile : g16_tile16(d), tile == 0, group, s, big, small);
+    // (the generic epilogue only: NP = 1 has no forms)
+    static const g16_kernel_t small[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, G16H_STAGES, 1>, nullptr, nullptr, nullptr};
+    static const g16_kernel_t big[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, G16H_STAGES, 1>, nullptr, nullptr, nullptr};
+    g16_launch16(d, (tile == 18 || tile == 22) ? tile : g16_tile16(d), tile == 0, group, s, big, small, false);
     return dupl_launch_status();
 }

@@ -133,7 +133,8 @@ class W16:
 # Launch tuning of the split GEMM (dupl_gemm16_desc.tile / concurrency / persist_blocks / group): per-call fields of the
 # descriptor since ABI 2.  This module-level dict holds the DEFAULTS (environment) for direct callers of linear16 (tests, tools); a
 # model carries its own copy (engine.FlatStorage.gemm16_tuning, handed to linear16 as `tuning`) -- model code never writes here.
-# concurrency: streams that issue split GEMMs at a time (siamese_network.enable_dual_stream sets 2 on ITS model); tile: DUPL_GEMM16_TILE.
+# concurrency: streams that issue split GEMMs at a time (siamese_network.enable_dual_stream sets 2 on ITS model); tile: DUPL_GEMM16_TILE
+# (the library validates the code: include/dupl_hip.h lists them; 28 / 30 / 32 = 18 / 22 / 26 with the generic epilogue walk forced).
 import os as _os
 GEMM16_TUNING = {"tile": int(_os.environ.get("DUPL_GEMM16_TILE", "0")), "concurrency": 1,
                  "persist_blocks": int(_os.environ.get("DUPL_PERSIST_BLOCKS", "0")), "group": 0,

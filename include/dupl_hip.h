@@ -133,7 +133,9 @@ typedef struct dupl_gemm16_desc {
                                              k-major operands (also in dupl_gemm_f16x3_group, where the last non-zero code of the group
                                              holds): 24: the 256x128 persistent kernels on v_mfma_f32_32x32x16_f16, 26: the same kernels on
                                              v_mfma_f32_16x16x32_f16 (differ in the last bits, as above); every other code, and 24 / 26
-                                             on k-contiguous operands, is the library's choice */
+                                             on k-contiguous operands, is the library's choice.  28 / 30 / 32: as 18 / 22 / 26 with the
+                                             generic epilogue walk forced instead of the compile-time epilogue form the launcher would
+                                             match the descriptor to (same bits; the A/B partner of the forms) */
     int32_t concurrency;                  /* how many streams issue split GEMMs at the same time (2 while the two students of
                                              siamese_network run on their own streams, model_dupl.py:157-213): tile heuristic input */
     int32_t persist_blocks;               /* blocks of the persistent kernels, a multiple of 8 (0: 256 alone, 192 at concurrency 2) */

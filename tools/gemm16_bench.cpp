@@ -11,7 +11,9 @@
 //             operands only; 5 has no counterpart in the reference kernel: its error column is not a check)
 //         -c: correctness only      -2: run every launch on two streams concurrently (the step's two students)
 //         -r: A/B mode -- the variants take turns, `rounds` times each (one process, one device); per variant the median and the minimum
-//             time per launch and the median shader clock of its timed regions (with -f: tiles 8 / 12 against 18 / 22)
+//             time per launch and the median shader clock of its timed regions (with -f: tiles 8 / 12 against 18 / 22; the epilogue
+//             forms: -t 28,18 / 30,22 with -e 1 | 2 | 3 and -L nk -t 32,26 with -e 5 | 6 -- 28 / 30 / 32 are 18 / 22 / 26 with the
+//             generic epilogue walk forced)
 //         -G: the grouped weight gradients of one transformer block (dupl_gemm_f16x3_group: 2304x768, 768x768, 3072x768, 768x3072 at K = 3168,
 //             written with DUPL_GEMM_C_FRESH) instead of the shapes of -s; -t 24,26 = the two kernel bodies, with -r and -2 as above
 //         Without -r a variant prints `t<tile> <TF/s-eq> <GHz> (<err>)`: the shader clock of the timed region is a column of its own, which

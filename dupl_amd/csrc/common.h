@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_fp16.h>
 #include <stdint.h>
+#include <cfloat>
 
 #define DUPL_OK 0
 #define DUPL_ERR_ARG (-1)
@@ -182,8 +183,8 @@ constexpr float DUPL_LO_SCALE = 2048.f;
 // f16 conversion for one of the two uses below (v_fma_mixlo_f16 on the exact product) but not for the other
 // (v_cvt_pk_f16_f32 of the fp32-rounded product): where the two roundings differ, `hi` and the residual behind `lo`
 // disagree by one fp16 ulp of hi -- a rare, data-dependent 2^-11 relative error (found in the dk kernel).
-// Range: finite |x| > 65504 saturates -- tensors that could get there are kept off this path by the range guard
-// (engine.RangeGuard, csrc/range.hip); NaN / Inf propagate as in fp32 arithmetic (hi = NaN / Inf, lo = NaN), they are not
+// Range: every finite |x| > 65504 saturates (up to FLT_MAX: the select below passes only NaN / Inf through) -- tensors that
+// could get there are kept off this path by the range guard (engine.RangeGuard, csrc/range.hip); NaN / Inf propagate as in fp32 arithmetic (hi = NaN / Inf, lo = NaN), they are not
 // laundered into finite values (fmaxf(NaN, a) = a would do that).
 // Format 1 of the operand planes (single-accumulator GEMM tiles): the value travels pre-scaled by a power of two chosen per
 // tensor class (X = x * 2^s: activations s = 3, weights s = 9) and lo = fp16(X - hi) WITHOUT the x 2048 -- all three products
@@ -192,14 +193,14 @@ constexpr float DUPL_LO_SCALE = 2048.f;
 // format is relative to the tensor's scale, not to each element (the range guard bounds the top end: |X| <= 65504).
 __device__ __forceinline__ void split_f32_u(float x, __half& hi, __half& lo) {
     const float c = fminf(fmaxf(x, -65504.f), 65504.f);
-    x = fabsf(x) <= 3.0e38f ? c : x;
+    x = fabsf(x) <= FLT_MAX ? c : x;
     asm volatile("" : "+v"(x));
     hi = __float2half_rn(x);
     lo = __float2half_rn(x - __half2float(hi));
 }
 __device__ __forceinline__ void split_f32(float x, __half& hi, __half& lo) {
     const float c = fminf(fmaxf(x, -65504.f), 65504.f);
-    x = fabsf(x) <= 3.0e38f ? c : x;
+    x = fabsf(x) <= FLT_MAX ? c : x;
     asm volatile("" : "+v"(x));
     hi = __float2half_rn(x);
     lo = __float2half_rn((x - __half2float(hi)) * DUPL_LO_SCALE);
@@ -214,7 +215,7 @@ __device__ __forceinline__ gelu_f32x2 split2_clamp(const gelu_f32x2 x) {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
         const float k = fminf(fmaxf(x[c], -65504.f), 65504.f);
-        r[c] = fabsf(x[c]) <= 3.0e38f ? k : x[c];
+        r[c] = fabsf(x[c]) <= FLT_MAX ? k : x[c];
     }
     asm volatile("" : "+v"(r));
     return r;

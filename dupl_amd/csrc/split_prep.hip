@@ -4,6 +4,8 @@
 // scaled by a power of two chosen from its own max-abs (amax * scale in [2^14, 2^15)), which is exact, keeps every
 // element within 2^-11 * 2^-25 of the tensor's largest one, and is undone by the GEMM epilogue (the inverse scale travels
 // through device memory: no host synchronisation).  Activations and weights are O(1) and are split unscaled.
+// Tiny-amax rule: the scale's exponent is clamped to [-126, 126] (scale_from_amax), so scale and inverse scale are always
+// finite, normal and exact inverses; a tensor with amax < 2^(target-127) is scaled by 2^126 and lands below the target.
 //
 // The backward GEMMs are cast as k-contiguous x k-contiguous products (the only layout gemm_split.hip implements):
 //   dgrad  dx[M][K] = dy[M][N] . W[N][K]          = dy16 [M][N] . (W^T16 [K][N])^T
@@ -31,17 +33,22 @@ __global__ __launch_bounds__(256) void amax_kernel(const float* __restrict__ x, 
     }
 }
 
-// scale = 2^(target - e), with amax in [2^(e-1), 2^e): amax * scale in [2^(target-1), 2^target)   (1 for amax == 0 /
-// non-finite).  target = 15 for GEMM operands; the attention backward uses 4 (dP = dO v^T is summed before its split).
+// scale = 2^k, 1 / scale = 2^-k with k = target - e clamped to [-126, 126], amax in [2^(e-1), 2^e): amax * scale in
+// [2^(target-1), 2^target) wherever target - e is within the clamp (1 for amax == 0 / non-finite).  The clamp keeps both
+// numbers normal fp32 powers of two with scale * (1 / scale) == 1 for EVERY amax: a tiny tensor (amax < 2^(target-127), about
+// 9.6e-35 for target 15; subnormals included) is scaled by 2^126 only and its planes stay below the target -- 2^(target - e)
+// itself is +Inf there, which made every non-zero element Inf in the planes and NaN in the data gradient.  The exponent is read
+// from the bits (a subnormal amax reads as e = -126: clamped either way).  tests/split_ref.py scale_rule is the specification.
+// target = 15 for GEMM operands; the attention backward uses 4 (dP = dO v^T is summed before its split).
 __device__ __forceinline__ void scale_from_amax(unsigned int bits, int target, float& s, float& inv) {
-    const float a = __uint_as_float(bits);
     s = 1.f;
     inv = 1.f;
-    if (a > 0.f && a < INFINITY) {
-        int e;
-        frexpf(a, &e);
-        s = ldexpf(1.f, target - e);
-        inv = ldexpf(1.f, e - target);
+    if (bits > 0u && bits < 0x7f800000u) {             // 0 < amax < Inf (the amax word is a non-negative float's bits)
+        const int e = (int)(bits >> 23) - 126;         // frexp's exponent of a normal amax
+        int k = target - e;
+        k = k > 126 ? 126 : (k < -126 ? -126 : k);
+        s = __uint_as_float((unsigned int)(127 + k) << 23);
+        inv = __uint_as_float((unsigned int)(127 - k) << 23);
     }
 }
 

@@ -166,7 +166,9 @@ int dupl_split_f16x2b(const float* x, void* hi, void* lo, int64_t n, int32_t sca
 /* operand preparation for the backward split GEMMs (csrc/split_prep.hip): x [R][ld] fp32 (C columns) -> row-major planes
  * hi / lo [R][C] and / or transposed planes hiT / loT [C][Rp] (Rp >= R, multiple of 8; rows R.. are zeros).
  * slot != NULL (gradients, far below fp16's normal range): the tensor is scaled by the power of two that brings its
- * max-abs into [2^(target_exp-1), 2^target_exp) (15 for GEMM operands); slot = 4 floats of device memory {scale, 1 / scale,
+ * max-abs into [2^(target_exp-1), 2^target_exp) (15 for GEMM operands) -- the power's exponent is clamped to [-126, 126], so
+ * scale and 1 / scale are normal fp32 powers of two with product 1 for every max-abs: a tiny tensor (max-abs < 2^(target_exp-127),
+ * subnormals included) is scaled by 2^126 only and stays below the target; max-abs 0 / Inf gives scale 1; slot = 4 floats of device memory {scale, 1 / scale,
  * amax word, -}; pass slot + 1 as the GEMM's alpha_dev.  next_bits (optional): the amax word of the slot the next scaled call
  * on this stream will use -- it is zeroed by this call (a ring of slots then needs no memset).
  * amax_mode: where the amax word of `slot` comes from -- 0 = this call computes it (the word must be zero on entry); 1 = the

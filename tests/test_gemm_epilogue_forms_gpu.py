@@ -260,7 +260,7 @@ def _split_ref(x, scale, fmt1):
     with np.errstate(all="ignore"):
         x = (x * np.float32(scale)).astype(np.float32) if fmt1 else x
         c = np.minimum(np.maximum(x, np.float32(-65504.0)), np.float32(65504.0))        # (fmaxf / fminf return the non-NaN operand ...
-        x = np.where(np.abs(x) <= np.float32(3.0e38), c, x).astype(np.float32)           #  ... but NaN and Inf pass through here)
+        x = np.where(np.abs(x) <= np.finfo(np.float32).max, c, x).astype(np.float32)  #  ... but NaN and Inf pass through here)
         hi = x.astype(np.float16)
         r = (x - hi.astype(np.float32)).astype(np.float32)
         lo = (r if fmt1 else (r * np.float32(2048.0)).astype(np.float32)).astype(np.float16)

@@ -201,6 +201,34 @@ class WindowMergeDesc(ctypes.Structure):
         self.struct_size = ctypes.sizeof(WindowMergeDesc)
 
 
+class SegRegionsDesc(ctypes.Structure):
+    """Mirror of `dupl_seg_regions_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32),
+        ("connectivity", ctypes.c_int32), ("ignore_index", ctypes.c_int32), ("max_regions", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+        ("label", ctypes.c_void_p), ("conf", ctypes.c_void_p), ("region", ctypes.c_void_p), ("n_regions", ctypes.c_void_p),
+        ("table", ctypes.c_void_p), ("stats", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(SegRegionsDesc)
+
+
+class SegRegionsCleanDesc(ctypes.Structure):
+    """Mirror of `dupl_seg_regions_clean_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("C", ctypes.c_int32),
+        ("max_regions", ctypes.c_int32), ("reserved0", ctypes.c_int32), ("min_area", ctypes.c_int64),
+        ("label", ctypes.c_void_p), ("region", ctypes.c_void_p), ("n_regions", ctypes.c_void_p), ("table", ctypes.c_void_p),
+        ("label_out", ctypes.c_void_p), ("changed", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(SegRegionsCleanDesc)
+
+
 GEMM_A_MCONTIG, GEMM_B_NCONTIG, GEMM_GELU, GEMM_ACCUM = 1, 2, 4, 8
 GEMM_MUL_DGELU, GEMM_RELU, GEMM_MUL_RELUMASK, GEMM_ABS, GEMM_STORE_PRE = 16, 32, 64, 128, 256
 GEMM_C_FRESH = 512            # DUPL_GEMM_C_FRESH (dupl_gemm_f16x3_group)
@@ -226,6 +254,7 @@ SEG_ENSEMBLE_MAX_C = 255      # DUPL_SEG_ENSEMBLE_MAX_C
 SEG_DECIDE_MAX_C = 255        # DUPL_SEG_DECIDE_MAX_C
 WINDOW_MAX = 256              # DUPL_WINDOW_MAX
 CRF_LATTICE_PIECE = 128       # DUPL_CRF_LATTICE_PIECE
+SEG_REGIONS_MAX_C, SEG_REGIONS_COLS = 256, 8  # DUPL_SEG_REGIONS_MAX_C, DUPL_SEG_REGIONS_COLS
 
 _PROTO = re.compile(r"^\s*int\s+(dupl_\w+)\s*\(([^;{]*)\)\s*;", re.M | re.S)
 
@@ -256,6 +285,10 @@ def _ctype(decl: str):
         return ctypes.POINTER(WindowGatherDesc)
     if "dupl_window_merge_desc" in d:
         return ctypes.POINTER(WindowMergeDesc)
+    if "dupl_seg_regions_desc" in d:
+        return ctypes.POINTER(SegRegionsDesc)
+    if "dupl_seg_regions_clean_desc" in d:
+        return ctypes.POINTER(SegRegionsCleanDesc)
     if "*" in d or d.startswith("dupl_stream_t"):
         return ctypes.c_void_p
     base = d.replace("const", "").split()
@@ -311,6 +344,10 @@ class _Lib:
         self.dupl_crf_lattice_workspace = self.cdll.dupl_crf_lattice_workspace
         self.dupl_crf_lattice_workspace.argtypes = [ctypes.POINTER(CrfLatticeDesc), ctypes.c_int32]
         self.dupl_crf_lattice_workspace.restype = ctypes.c_int64
+        for name, desc in (("dupl_seg_regions_workspace", SegRegionsDesc), ("dupl_seg_regions_clean_workspace", SegRegionsCleanDesc)):
+            fn = getattr(self.cdll, name)
+            fn.argtypes, fn.restype = [ctypes.POINTER(desc)], ctypes.c_int64
+            setattr(self, name, fn)
         from .build import source_digest, _sources
         if _sources() and os.environ.get("DUPL_SKIP_DIGEST_CHECK", "0") != "1":
             have = source_digest()

@@ -1363,3 +1363,102 @@ def window_merge(logits: Tensor, origins, hs: int, ws: int) -> Tensor:
                              origins=org.ctypes.data, canvas=out.data_ptr())
     L().dupl_window_merge(ctypes.byref(d), _stream())
     return out
+
+
+# ------------------------------------------------------------------------------------------ connected regions (csrc/regions.hip)
+def _regions_classes(stats: Optional[Tensor], num_classes: Optional[int]) -> int:
+    if stats is not None:
+        assert stats.is_cuda and stats.dtype == torch.int64 and stats.is_contiguous() and stats.dim() == 2 and stats.shape[0] == 2, \
+            f"stats must be (2, C + 1) int64, got {tuple(stats.shape)}"
+        if num_classes is not None and int(num_classes) != stats.shape[1] - 1:
+            raise ValueError(f"num_classes {num_classes} does not match stats of {stats.shape[1] - 1} classes")
+        num_classes = stats.shape[1] - 1
+    C = _lib.SEG_REGIONS_MAX_C if num_classes is None else int(num_classes)
+    if not 1 <= C <= _lib.SEG_REGIONS_MAX_C:
+        raise ValueError(f"seg_regions takes 1 .. {_lib.SEG_REGIONS_MAX_C} classes, got {C}")
+    return C
+
+
+def _seg_regions(label: Tensor, conf: Optional[Tensor], connectivity: int, ignore_index: int, max_regions: int,
+                 stats: Optional[Tensor], C: int):
+    """one dupl_seg_regions call -> (region, n_regions as a device tensor, the whole table)"""
+    assert label.is_cuda and label.dtype == torch.uint8 and label.dim() == 2 and label.is_contiguous(), "label: a contiguous (H,W) uint8 device tensor"
+    H, W = label.shape
+    if H < 1 or W < 1:
+        raise ValueError(f"seg_regions needs at least one pixel, got {(H, W)}")
+    if int(connectivity) not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
+    if not 0 <= int(ignore_index) <= 255:
+        raise ValueError(f"ignore_index must be 0 .. 255, got {ignore_index}")
+    if int(max_regions) < 1:
+        raise ValueError(f"max_regions must be at least 1, got {max_regions}")
+    if conf is not None:
+        assert tuple(conf.shape) == (H, W), f"conf must be {(H, W)}, got {tuple(conf.shape)}"
+        conf = _chk(conf)
+    dev = label.device
+    rows = min(int(max_regions), H * W)
+    region = torch.empty((H, W), device=dev, dtype=torch.int32)
+    n = torch.empty((1,), device=dev, dtype=torch.int32)
+    table = torch.empty((rows, _lib.SEG_REGIONS_COLS), device=dev, dtype=torch.int64)
+    d = _lib.SegRegionsDesc(H=H, W=W, C=C, connectivity=int(connectivity), ignore_index=int(ignore_index), max_regions=rows,
+                            label=label.data_ptr(), conf=_p(conf), region=region.data_ptr(), n_regions=n.data_ptr(),
+                            table=table.data_ptr(), stats=_p(stats))
+    nbytes = L().dupl_seg_regions_workspace(ctypes.byref(d))
+    assert nbytes > 0
+    ws = torch.empty((nbytes // 8 + 1,), device=dev, dtype=torch.int64)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    L().dupl_seg_regions(ctypes.byref(d), _stream())
+    return region, n, table
+
+
+def seg_regions(label: Tensor, conf: Optional[Tensor] = None, *, connectivity: int = 8, ignore_index: int = 255,
+                max_regions: int = 65536, stats: Optional[Tensor] = None, num_classes: Optional[int] = None):
+    """Connected regions of label (H,W) uint8 on the device (csrc/regions.hip): pixels are connected when they carry the same label
+    and are 4- / 8-neighbours; pixels equal to ignore_index (or >= the number of classes: stats' C, num_classes, 256 by default)
+    belong to no region.  Regions are numbered in raster order of their first pixel.
+      region (H,W) int32: the id, -1 on ignored pixels -- complete whatever max_regions is;
+      n_regions: a Python int, the true total -- reading it is the ONE synchronisation with the device this call makes;
+      table (min(n_regions, max_regions), 8) int64: class, area, y0, x0, y1, x1 (inclusive), conf_sum, first_index; conf_sum is the
+        sum of rint(conf * 2^24) over the region (seg_decide's fixed point; 0 without conf);
+      stats (2, C+1) int64 += seg_decide's per-label counts and conf sums, slot C the ignored pixels.
+    Returns (region, n_regions, table)."""
+    C = _regions_classes(stats, num_classes)
+    region, n, table = _seg_regions(label, conf, connectivity, ignore_index, max_regions, stats, C)
+    n = int(n.item())
+    return region, n, table[:min(n, table.shape[0])]
+
+
+def seg_regions_clean(label: Tensor, *, min_area: int, connectivity: int = 8, ignore_index: int = 255, max_regions: int = 65536,
+                      conf: Optional[Tensor] = None, stats: Optional[Tensor] = None):
+    """Absorb the regions of label (H,W) uint8 with fewer than min_area pixels: label the map, give every small region the class most
+    of its 4-neighbour pixels in kept (area >= min_area) regions carry (first maximum wins; no such neighbour: unchanged; one pass,
+    decided on the input map; ignored pixels neither vote nor change), and label the result again.
+    Returns (label_out, region, n_regions, table, changed): label_out a new (H,W) uint8 map, region / n_regions / table as
+    seg_regions returns them for label_out (conf and stats go to that second labelling: everything describes the cleaned map),
+    changed (2,) int64 on the device: regions and pixels relabelled.  Raises ValueError when the first labelling finds more than
+    max_regions regions: no partly cleaned map is handed back.  Synchronises with the device twice (the two region counts)."""
+    if int(min_area) < 0:
+        raise ValueError(f"min_area must be at least 0, got {min_area}")
+    C = _regions_classes(stats, None)
+    region, n_dev, table = _seg_regions(label, None, connectivity, ignore_index, max_regions, None, C)
+    n = int(n_dev.item())
+    if n > int(max_regions):
+        raise ValueError(f"seg_regions_clean: the map has {n} regions, more than max_regions = {max_regions}")
+    H, W = label.shape
+    dev = label.device
+    out = torch.empty((H, W), device=dev, dtype=torch.uint8)
+    changed = torch.zeros((2,), device=dev, dtype=torch.int64)
+    if n == 0:
+        out.copy_(label)
+    else:
+        d = _lib.SegRegionsCleanDesc(H=H, W=W, C=C, max_regions=n, min_area=int(min_area), label=label.data_ptr(),
+                                     region=region.data_ptr(), n_regions=n_dev.data_ptr(), table=table.data_ptr(),
+                                     label_out=out.data_ptr(), changed=changed.data_ptr())
+        nbytes = L().dupl_seg_regions_clean_workspace(ctypes.byref(d))
+        assert nbytes > 0
+        ws = torch.empty((nbytes // 8 + 1,), device=dev, dtype=torch.int64)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        L().dupl_seg_regions_clean(ctypes.byref(d), _stream())
+    region, n, table = seg_regions(out, conf, connectivity=connectivity, ignore_index=ignore_index, max_regions=max_regions,
+                                   stats=stats, num_classes=C)
+    return out, region, n, table, changed

@@ -7,8 +7,10 @@ Per image: the multi-scale + flip inference of tools/eval_seg (`msc_seg_logits`)
 (`msc_seg_logits_windowed`: ops.window_gather cuts the windows of the resized image and of its flip straight from the source, the two
 students run on chunks of `window_batch` windows, ops.window_merge averages the overlapping logits on the canvas that
 ops.msc_seg_accum_ consumes), optionally DenseCRF, then ONE pass that turns the logits into the label map, the per-pixel confidence,
-the rejection of low-confidence pixels and the per-class statistics (ops.seg_decide), and one integer pass for the palette overlay
-(ops.seg_paint).  Nothing but the PNGs' pixels and 2 (C+1) counters travel to the host."""
+the rejection of low-confidence pixels and the per-class statistics (ops.seg_decide), optionally the connected regions of that map (ops.seg_regions: --regions 1 lists the objects with class, area, box
+and mean confidence; --min_region N first absorbs the regions of fewer than N pixels into their surroundings,
+ops.seg_regions_clean), and one integer pass for the palette overlay (ops.seg_paint).  Nothing but the PNGs' pixels, 2 (C+1)
+counters and, when asked for, the region table travel to the host."""
 import argparse
 import json
 import os
@@ -133,12 +135,16 @@ def device_palette(dev):
 
 def predict_image(model, image_u8, *, scales=(1.0, 1.5, 1.25), branch="ens", window=0, stride=0, window_batch=8, crf=False,
                   min_conf=0.0, ignore_index=255, alpha=0.6, contour=False, tint_background=False, contour_rgb=(255, 255, 255),
-                  crf_method="exact"):
+                  crf_method="exact", min_region=0, regions=False, connectivity=8, max_regions=4096):
     """image_u8 (H,W,3) uint8 (numpy or tensor) -> dict(label (H,W) uint8, conf (H,W) fp32, overlay (H,W,3) uint8 -- device tensors --,
     stats (2, C+1) int64 on the host: ops.seg_decide's, windows: the windows per scale).  branch 1 / 2: that student, "ens": the
     mean of the two students' class probabilities.  crf: DenseCRF with crf_proc's parameters on the chosen student's logits or on
     the ensemble's probabilities, then the decision on its marginals; crf_method "exact" (the dense mean-field update) or "lattice"
-    (the permutohedral approximation, utils/dcrf.py)."""
+    (the permutohedral approximation, utils/dcrf.py).
+    min_region > 0: the connected regions (connectivity 4 / 8) of fewer than min_region pixels are absorbed by their surroundings
+    (ops.seg_regions_clean) before painting; label, overlay and stats then describe the cleaned map (the rejected pixels stay), and
+    `cleaned` = {regions, pixels} says what moved.  regions: also region (H,W) int32 (device), n_regions and region_table, the first
+    max_regions rows of ops.seg_regions's table on the host.  With neither, the dict has the keys above and no region op runs."""
     from ..datasets.device_loader import DeviceTransform
     from ..utils.train_helper import _device_of
     branch = str(branch)
@@ -146,6 +152,12 @@ def predict_image(model, image_u8, *, scales=(1.0, 1.5, 1.25), branch="ens", win
         raise ValueError(f"branch must be 1, 2 or ens, got {branch}")
     if crf_method not in ("exact", "lattice"):
         raise ValueError(f"crf_method must be exact or lattice, got {crf_method}")
+    if int(min_region) < 0:
+        raise ValueError(f"min_region must be at least 0, got {min_region}")
+    if int(connectivity) not in (4, 8):
+        raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
+    if int(max_regions) < 1:
+        raise ValueError(f"max_regions must be at least 1, got {max_regions}")
     if window and not stride:
         stride = default_stride(window)
     check_window_args(window, stride)
@@ -172,10 +184,24 @@ def predict_image(model, image_u8, *, scales=(1.0, 1.5, 1.25), branch="ens", win
         label, conf = ops.seg_decide(seg[0], seg[1], **kw)
     else:
         label, conf = ops.seg_decide(seg[int(branch) - 1], **kw)
+    extra = {}
+    if int(min_region) > 0:
+        # the cleaned map's statistics replace the decision's; the regions are counted in full here (the cap is on the list only)
+        stats = torch.zeros((2, C + 1), device=dev, dtype=torch.int64)
+        label, region, n, table, changed = ops.seg_regions_clean(label, min_area=int(min_region), connectivity=connectivity,
+                                                                 ignore_index=ignore_index, max_regions=H * W, conf=conf, stats=stats)
+        changed = changed.cpu()
+        extra["cleaned"] = {"regions": int(changed[0]), "pixels": int(changed[1])}
+        if regions:
+            extra.update(region=region, n_regions=n, region_table=table[:int(max_regions)].cpu())
+    elif regions:
+        region, n, table = ops.seg_regions(label, conf, connectivity=connectivity, ignore_index=ignore_index,
+                                           max_regions=int(max_regions), num_classes=C)
+        extra.update(region=region, n_regions=n, region_table=table.cpu())
     overlay = ops.seg_paint(label, device_palette(dev), raw, alpha256=int(round(float(alpha) * 256)), tint_background=tint_background,
                             contour=contour, contour_rgb=contour_rgb)
     return {"label": label, "conf": conf, "overlay": overlay, "stats": stats.cpu(),
-            "windows": windows_per_scale(H, W, scales, window, stride)}
+            "windows": windows_per_scale(H, W, scales, window, stride), **extra}
 
 
 def class_summary(stats, names, n_pixels):
@@ -189,6 +215,18 @@ def class_summary(stats, names, n_pixels):
             out.append({"id": c, "name": names[c] if c < len(names) else f"class{c}", "pixels": n, "share": n / n_pixels,
                         "mean_conf": int(st[1, c]) / float(1 << 24) / n})
     return out, int(st[0, C])
+
+
+def region_summary(table, names, min_pixels=1):
+    """rows of ops.seg_regions's table (class, area, y0, x0, y1, x1, conf_sum, first_index) -> [{id, class, name, pixels,
+    box: [x0, y0, x1, y1] (inclusive), mean_conf} per region of at least min_pixels pixels], in id order."""
+    out = []
+    for i, row in enumerate(np.asarray(table, dtype=np.int64).reshape(-1, 8)):
+        c, n = int(row[0]), int(row[1])
+        if n >= int(min_pixels):
+            out.append({"id": i, "class": c, "name": names[c] if c < len(names) else f"class{c}", "pixels": n,
+                        "box": [int(row[3]), int(row[2]), int(row[5]), int(row[4])], "mean_conf": int(row[6]) / float(1 << 24) / n})
+    return out
 
 
 def class_names(spec):
@@ -241,6 +279,14 @@ def build_parser():
     p.add_argument("--nograd_gemm", default=os.environ.get("DUPL_NOGRAD_GEMM", "f16x3"), choices=("f16x3", "f16"),
                    help="GEMMs and attention of the no-grad encoder passes: f16x3 = three f16 products, fp32-equivalent (default); "
                         "f16 = one product on the hi planes (engine.set_nograd_gemm_mode; experimental)")
+    p.add_argument("--min_region", default=0, type=int, help="absorb connected regions of fewer than N pixels into their surroundings "
+                                                             "before painting; 0 = off")
+    p.add_argument("--regions", default=0, type=int, choices=(0, 1), help="1: list the connected regions (class, pixels, box, mean "
+                                                                          "confidence) per image in summary.json")
+    p.add_argument("--region_min_pixels", default=1, type=int, help="--regions 1: list only regions of at least this many pixels")
+    p.add_argument("--max_regions", default=4096, type=int, help="--regions 1: cap on the regions listed per image (regions_total "
+                                                                 "still gives the true count)")
+    p.add_argument("--connectivity", default=8, type=int, choices=(4, 8), help="pixel neighbourhood of --min_region and --regions")
     p.add_argument("--save_conf", default=0, type=int, choices=(0, 1), help="1: also write conf/<stem>.png = floor(255 conf)")
     return p
 
@@ -265,6 +311,12 @@ def parse_args(argv=None):
         raise SystemExit(f"--alpha must lie in 0 .. 1, got {args.alpha}")
     if not 1 <= args.num_classes <= 255:
         raise SystemExit(f"--num_classes must be 1 .. 255 (the label PNG keeps 255 for rejected pixels), got {args.num_classes}")
+    if args.min_region < 0:
+        raise SystemExit(f"--min_region must be at least 0, got {args.min_region}")
+    if args.region_min_pixels < 1:
+        raise SystemExit(f"--region_min_pixels must be at least 1, got {args.region_min_pixels}")
+    if args.max_regions < 1:
+        raise SystemExit(f"--max_regions must be at least 1, got {args.max_regions}")
     return args
 
 
@@ -295,7 +347,9 @@ def main(argv=None):
         H, W, _ = image.shape
         r = predict_image(model, image, scales=args.scales, branch=args.branch, window=args.window, stride=args.stride,
                           window_batch=args.window_batch, crf=bool(args.crf), min_conf=args.min_conf, alpha=args.alpha,
-                          contour=bool(args.contour), tint_background=bool(args.tint_background), crf_method=args.crf_method)
+                          contour=bool(args.contour), tint_background=bool(args.tint_background), crf_method=args.crf_method,
+                          **({"min_region": args.min_region, "regions": bool(args.regions), "connectivity": args.connectivity,
+                              "max_regions": args.max_regions} if args.min_region or args.regions else {}))
         png = Image.fromarray(r["label"].cpu().numpy())        # mode L; attaching the palette makes it an index image (mode P)
         png.putpalette(flat_palette)
         png.save(os.path.join(args.out_dir, "labels", stem + ".png"))
@@ -306,14 +360,25 @@ def main(argv=None):
         classes, rejected = class_summary(r["stats"], names, H * W)
         summary.append({"image": os.path.basename(path), "size": [H, W], "windows_per_scale": r["windows"], "classes": classes,
                         "rejected_pixels": rejected})
+        if args.min_region:
+            summary[-1].update(min_region=args.min_region, cleaned=r["cleaned"])
         found = ", ".join(f"{c['name']} {100 * c['share']:.1f}%" for c in classes)
         print(f"{os.path.basename(path)}: {H}x{W}, windows {r['windows']}, {found}; rejected {rejected}")
+        if args.regions:
+            summary[-1].update(regions_total=r["n_regions"], regions=region_summary(r["region_table"], names, args.region_min_pixels))
+            tab = r["region_table"].numpy()
+            per = np.bincount(tab[:, 0], minlength=1)[1:] if len(tab) else []
+            listed = ", ".join(f"{names[c + 1] if c + 1 < len(names) else f'class{c + 1}'} {int(k)}" for c, k in enumerate(per) if k)
+            print(f"{os.path.basename(path)}: {r['n_regions']} regions" + (f" ({listed})" if listed else ""))
     torch.cuda.synchronize()
     dt = time.time() - t0
     with open(os.path.join(args.out_dir, "summary.json"), "w") as f:
         json.dump({"scales": list(args.scales), "branch": args.branch, "window": args.window, "stride": args.stride if args.window else 0,
                    "crf": int(args.crf), **({"crf_method": args.crf_method} if args.crf_method_given else {}),
-                   "min_conf": args.min_conf, "images": summary}, f, indent=1)
+                   "min_conf": args.min_conf,
+                   **({"min_region": args.min_region, "cleaned": {k: sum(e["cleaned"][k] for e in summary) for k in ("regions", "pixels")}}
+                      if args.min_region else {}),
+                   "images": summary}, f, indent=1)
     print(f"{len(paths)} images in {dt:.2f} s: {len(paths) / dt:.2f} images/s")
     return summary
 

@@ -852,6 +852,72 @@ typedef struct dupl_window_merge_desc {
 } dupl_window_merge_desc;
 int dupl_window_merge(const dupl_window_merge_desc* d, dupl_stream_t stream);
 
+/* ------------------------------------------------------------------ connected regions of a label map (csrc/regions.hip)
+ * Two pixels are connected when they carry the same label and are 4- or 8-neighbours (`connectivity`).  Pixels whose label is
+ * ignore_index, or >= C, belong to no region.  The result is canonical: the representative of a region is its first pixel in raster
+ * order (smallest y W + x), and regions are numbered 0 .. n-1 in raster order of that pixel, across all classes together.
+ *   region (H,W) int32: the region id, -1 on ignored pixels; always complete, whatever max_regions is;
+ *   n_regions int32[1]: the true total, whatever max_regions is;
+ *   table (max_regions, 8) int64: class, area, y0, x0, y1, x1 (inclusive box), conf_sum, first_index of regions
+ *                       0 .. min(n, max_regions) - 1; the other rows are not touched.  conf_sum = the sum of
+ *                       (int64)rintf(conf * 2^24) over the region (dupl_seg_decide's definition), 0 without conf;
+ *   stats (2, C+1) int64, ADDED to: dupl_seg_decide's layout -- row 0 the pixels per label with slot C for the ignored ones, row 1
+ *                       the conf sums of the same pixels (nothing is added to row 1 without conf).
+ * Every output is optional, at least one is required.  Integer atomics only, combined per workgroup first: bit-reproducible, and a
+ * region that covers the image costs no more than many small ones.  Scratch: `workspace` of at least dupl_seg_regions_workspace(d)
+ * bytes, 8-byte aligned; its contents before and after the call mean nothing. */
+#define DUPL_SEG_REGIONS_MAX_C 256
+#define DUPL_SEG_REGIONS_COLS 8
+typedef struct dupl_seg_regions_desc {
+    uint32_t struct_size;        /* sizeof(dupl_seg_regions_desc), checked */
+    int32_t H, W;                /* >= 1 each, H W < 2^31 - 16 */
+    int32_t C;                   /* 1 .. DUPL_SEG_REGIONS_MAX_C: labels >= C count as ignored */
+    int32_t connectivity;        /* 4 or 8 */
+    int32_t ignore_index;        /* 0 .. 255 */
+    int32_t max_regions;         /* rows of table; >= 1 with a table */
+    int32_t reserved0;           /* 0 */
+    const uint8_t* label;        /* (H,W), any byte address */
+    const float* conf;           /* (H,W); or NULL */
+    int32_t* region;             /* (H,W); or NULL */
+    int32_t* n_regions;          /* [1]; or NULL */
+    int64_t* table;              /* (max_regions, 8); or NULL */
+    int64_t* stats;              /* (2, C+1); or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+} dupl_seg_regions_desc;
+/* bytes of scratch the call needs, from H and W: 8 H W + 4 (H W / 1024 + 2), each part rounded up to 256; <= 0 on a bad descriptor */
+int64_t dupl_seg_regions_workspace(const dupl_seg_regions_desc* d);
+int dupl_seg_regions(const dupl_seg_regions_desc* d, dupl_stream_t stream);
+
+/* Absorb the small regions of a labelling (region, n_regions, table as dupl_seg_regions wrote them for `label`) into their
+ * surroundings, in one pass decided entirely on the input map:
+ *   a region is kept when area >= min_area, otherwise small -- decided exactly for every region, also for those without a table row;
+ *   votes[c] of a small region r = the number of pairs (p, q), p in r, q a 4-neighbour of p inside the image (always 4, whatever
+ *   connectivity the labelling used), q in a kept region of class c;  r takes the class with the most votes, the first maximum
+ *   wins; with no vote at all r keeps its class.  Ignored pixels never vote and never change.  Small regions with
+ *   id >= max_regions are left as they are.
+ * label_out (H,W) = label except on the pixels of relabelled regions; it may be `label` itself.  changed int64[2] is WRITTEN:
+ * regions relabelled, pixels relabelled.  Scratch as above, see dupl_seg_regions_clean_workspace. */
+typedef struct dupl_seg_regions_clean_desc {
+    uint32_t struct_size;        /* sizeof(dupl_seg_regions_clean_desc), checked */
+    int32_t H, W;
+    int32_t C;                   /* 1 .. DUPL_SEG_REGIONS_MAX_C, as in the labelling call */
+    int32_t max_regions;         /* rows of table, >= 1 */
+    int32_t reserved0;           /* 0 */
+    int64_t min_area;            /* >= 0; 0 and 1 change nothing */
+    const uint8_t* label;        /* (H,W) */
+    const int32_t* region;       /* (H,W) */
+    const int32_t* n_regions;    /* [1], device memory */
+    const int64_t* table;        /* (max_regions, 8) */
+    uint8_t* label_out;          /* (H,W) */
+    int64_t* changed;            /* [2] */
+    void* workspace;
+    int64_t workspace_bytes;
+} dupl_seg_regions_clean_desc;
+/* 4 (rows C + H W) bytes with rows = min(max_regions, H W), each part rounded up to 256; <= 0 on a bad descriptor */
+int64_t dupl_seg_regions_clean_workspace(const dupl_seg_regions_clean_desc* d);
+int dupl_seg_regions_clean(const dupl_seg_regions_clean_desc* d, dupl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd | seg_render | predict | crf_lattice
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd | seg_render | predict | crf_lattice | regions
 `crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81.
 `cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces.
 `seg_ensemble` (only when named) times the fused ensemble tail of tools/eval_seg --ensemble 1 (ops.seg_ensemble) against the composition
@@ -8,6 +8,9 @@ of existing ops that yields the same matrices, at the VOC and the COCO form.
 alternating in one process, at 375x500x21 and 480x640x81 (construction and iterations apart; a uniform-colour and a noise image too).
 `seg_render` (only when named; then nothing else runs) times ops.seg_decide against the composition of existing ops that yields the
 same label and confidence (VOC and COCO form, one and two students) and ops.seg_paint against the host palette-and-blend.
+`regions` (only when named; then nothing else runs) times ops.seg_regions and ops.seg_regions_clean (min_area 64) against the host path
+(label.cpu() -> scipy.ndimage.label per class -> find_objects -> bincount) on a VOC-sized and a 1024 x 2048 prediction-like map and on
+a 1024 x 2048 single-label map, after asserting that ids, areas and boxes agree.
 `predict` (only when named; then nothing else runs) times tools/predict on one synthetic 1024 x 2048 image, ViT-B, whole image against
 sliding windows, with the peak device memory of each.
 `backbone` (only when named; then nothing else runs) times one phase-B training step at VOC 448^2, 4 images, two student streams
@@ -264,6 +267,97 @@ def seg_render_bench(dev, g):
                   f"palette only {t_p:.1f} us; host numpy palette + blend {t_h:.0f} us ({t_h / t_o:.0f}x)")
 
 
+def regions_bench(dev, g):
+    """ops.seg_regions (region map + count + table with conf sums + stats: every launch, the count's read-back included) and
+    ops.seg_regions_clean (min_area 64: label, clean, label again) against what users do today: label.cpu(), scipy.ndimage.label per
+    class present (8-connectivity), find_objects, np.bincount.  (a), (b): a smooth seeded field plus 0.5 % seeded speckle, C = 21;
+    (c) one label everywhere -- every pixel lands on one table row.  Floor: 5 B/px (label in, region map out).  The launches of
+    one call, timed apart on (b), say what sets the time."""
+    import time
+    import numpy as np
+    from scipy import ndimage
+
+    def blobs(H, W):
+        up = torch.nn.functional.interpolate(torch.randn((1, 21, H // 24 + 2, W // 24 + 2), generator=g), size=(H, W), mode="bilinear",
+                                             align_corners=False)
+        lab = up[0].argmax(0).to(torch.uint8)
+        speck = torch.rand((H, W), generator=g) < 0.005
+        lab[speck] = torch.randint(0, 21, (H, W), generator=g, dtype=torch.uint8)[speck]
+        return lab
+
+    def host(label_dev):
+        lab = label_dev.cpu().numpy()
+        found = []
+        for c in np.unique(lab):
+            m, k = ndimage.label(lab == c, np.ones((3, 3), int))
+            area = np.bincount(m.ravel(), minlength=k + 1)[1:]
+            ids, at = np.unique(m.ravel(), return_index=True)       # the first pixel of every component, in raster order
+            first = np.zeros(k + 1, np.int64)
+            first[ids] = at
+            for j, sl in enumerate(ndimage.find_objects(m)):
+                found.append((int(first[j + 1]), int(c), int(area[j]), sl[0].start, sl[1].start, sl[0].stop - 1, sl[1].stop - 1))
+        return sorted(found)
+
+    def host_timed(label_dev):        # the same without the first-pixel bookkeeping that only the comparison needs
+        lab = label_dev.cpu().numpy()
+        n = 0
+        for c in np.unique(lab):
+            m, k = ndimage.label(lab == c, np.ones((3, 3), int))
+            ndimage.find_objects(m)
+            np.bincount(m.ravel(), minlength=k + 1)
+            n += k
+        return n
+
+    for name, label in (("(a) 375x500 blobs + speckle", blobs(375, 500)), ("(b) 1024x2048 blobs + speckle", blobs(1024, 2048)),
+                        ("(c) 1024x2048 one label", torch.full((1024, 2048), 7, dtype=torch.uint8))):
+        label = label.to(dev)
+        H, W = label.shape
+        conf = torch.rand((H, W), generator=g).to(dev)
+        stats = torch.zeros((2, 22), device=dev, dtype=torch.int64)
+        region, n, table = ops.seg_regions(label, conf, stats=stats)
+        want = host(label)
+        t = table.cpu().numpy()
+        assert n == len(want) == t.shape[0], (n, len(want))
+        assert [(int(r[7]), int(r[0]), int(r[1]), int(r[2]), int(r[3]), int(r[4]), int(r[5])) for r in t] == want
+        reg = region.cpu().numpy()
+        assert np.array_equal(reg.ravel()[t[:, 7]], np.arange(n)) and np.array_equal(np.bincount(reg.ravel(), minlength=n), t[:, 1])
+        t0 = time.perf_counter()
+        for _ in range(3):
+            host_timed(label)
+        t_h = (time.perf_counter() - t0) / 3 * 1e6
+        floor = 5 * H * W
+        for i in range(2):
+            t_r = timeit(lambda: ops.seg_regions(label, conf, stats=stats), n=100, warm=10)
+            t_m = timeit(lambda: ops.seg_regions(label), n=100, warm=10)
+            t_c = timeit(lambda: ops.seg_regions_clean(label, min_area=64, conf=conf, stats=stats), n=50, warm=5)
+            print(f"regions {name}, {n} regions, round {i}: seg_regions {t_r:.1f} us ({t_r * 1e3 / (H * W):.3f} ns/px; floor {floor / 1e6:.2f} MB = "
+                  f"{floor / 5.0e6:.1f} us at 5 TB/s, {floor / t_r / 1e6:.3f} TB/s of it), without conf and stats {t_m:.1f} us; "
+                  f"seg_regions_clean(64) {t_c:.1f} us; host scipy path {t_h:.0f} us ({t_h / t_r:.0f}x seg_regions)")
+    # where the time of one call on (b) and (c) goes: the launches between two events each, 50 calls
+    for name, label in (("(b)", blobs(1024, 2048).to(dev)), ("(c)", torch.full((1024, 2048), 7, dtype=torch.uint8, device=dev))):
+        H, W = label.shape
+        conf = torch.rand((H, W), generator=g).to(dev)
+        stats = torch.zeros((2, 22), device=dev, dtype=torch.int64)
+        t_all = timeit(lambda: ops._seg_regions(label, conf, 8, 255, 65536, stats, 21), n=100, warm=10)
+        t_n = timeit(lambda: _count_only(label), n=100, warm=10)
+        print(f"regions {name} without the read-back: all six launches {t_all:.1f} us; local + seam + flatten + scan alone (n_regions only) "
+              f"{t_n:.1f} us; number + stats {t_all - t_n:.1f} us")
+
+
+def _count_only(label):
+    """dupl_seg_regions asked for n_regions alone: the labelling launches without number and stats"""
+    import ctypes
+    from dupl_amd import _lib
+    H, W = label.shape
+    n = torch.empty((1,), device=label.device, dtype=torch.int32)
+    d = _lib.SegRegionsDesc(H=H, W=W, C=21, connectivity=8, ignore_index=255, max_regions=0, label=label.data_ptr(), n_regions=n.data_ptr())
+    nbytes = ops.L().dupl_seg_regions_workspace(ctypes.byref(d))
+    ws = torch.empty((nbytes // 8 + 1,), device=label.device, dtype=torch.int64)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+    ops.L().dupl_seg_regions(ctypes.byref(d), ops._stream())
+    return n
+
+
 def predict_bench(argv):
     """tools/predict on one synthetic 1024 x 2048 image, ViT-B (seeded random weights), scales 1.0 / 1.5 / 1.25: the whole image per
     scale against sliding windows (window=448 stride=320 window_batch=8), ms per image and peak device memory.
@@ -377,6 +471,8 @@ def main():
         return predict_bench(sys.argv[1:])
     if "seg_render" in sys.argv[1:]:
         return seg_render_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
+    if "regions" in sys.argv[1:]:
+        return regions_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     if "crf_lattice" in sys.argv[1:]:
         return crf_lattice_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}

@@ -12,7 +12,10 @@
   7  the exact-f32 kernels (yardstick of every f16x3 bar, product path of the backward beyond 2 048 tokens) at those lengths
 
 Bars are the project's standing ones (test_attention_fwd16_is_fp32_equivalent, test_attention_bwd16_is_fp32_equivalent,
-test_attention_fwd_bwd); every test prints its measured errors next to the exact-f32 kernel's before it asserts.
+test_attention_fwd_bwd); every test prints its measured errors next to the exact-f32 kernel's before it asserts.  The exact-f32
+kernel's own error is first held to ITS standing bars (out 5e-6, lse 5e-6, dqkv 2e-5 of the reference's maximum) on the same
+input, so a bar of the form "2 x the exact-f32 kernel's error" cannot widen unnoticed; the f32 kernels' own edges:
+tests/test_attention_f32_gpu.py.
 
 Cost on one MI355X, measured in one session: this module alone 4.4 s (92 tests; the slowest single test 0.9 s, the float64
 references run on the device); the whole -m gpu suite 639 s without it (325 tests) and 617 s with it (417 tests) -- the
@@ -91,6 +94,8 @@ def _fwd_bars(tag, out, lse, o32, lse32, ref, ref_lse):
     print(f"{tag}: out f16x3 {e16:.2e} f32 {e32:.2e} (bar {2.0 * e32 + 2e-7:.2e}); lse f16x3 {l16:.2e} f32 {l32:.2e} "
           f"(bar {2.0 * l32 + 1e-6:.2e})")
     assert torch.isfinite(out).all() and torch.isfinite(lse).all()
+    # the yardstick itself first: the exact-f32 kernel meets its own standing bars (test_attention_fwd_bwd) on this input
+    assert e32 < 5e-6 and l32 < 5e-6 * float(ref_lse.abs().max()), f"{tag}: the exact-f32 kernel misses its own bar"
     assert e16 <= 2.0 * e32 + 2e-7, tag
     assert l16 <= 2.0 * l32 + 1e-6, tag
     return sc
@@ -185,6 +190,10 @@ def _bwd_compare(dev, tag, B, N, H, qkv, dout):
     lse16 = ops.attention_fwd16(qkv16, B, N, H, HD, SCALE, need_lse=True, out=out16)
     d16 = ops.attention_bwd16(qkv16, out16, dout, lse16, B, N, H, HD, SCALE)
     assert torch.isfinite(d16).all()
+    # the yardstick itself first: the exact-f32 backward meets its own standing bar (test_attention_fwd_bwd) on this input
+    g32 = float((d32.double() - ref).abs().max() / ref.abs().max())
+    print(f"{tag}: exact-f32 dqkv {g32:.2e} of the reference's maximum (bar 2e-05)")
+    assert g32 < 2e-5, f"{tag}: the exact-f32 kernels miss their own bar"
     sc_dv = float(ref[:, 2 * D:].abs().max())
     for name, sl in (("dq", slice(0, D)), ("dk", slice(D, 2 * D)), ("dv", slice(2 * D, 3 * D))):
         sc = float(ref[:, sl].abs().max())

@@ -1353,22 +1353,13 @@ def test_gelu_epilogues_follow_the_header_formula(dev):
     pre-activations as the header's formula gives it in fp32 (coefficients parsed from the header; the Horner chain with one rounding
     per fused multiply-add, exp2 in double then rounded -- v_exp_f32 is within 1 ulp of that) -- and likewise dy * gelu'(pre) for the
     data-gradient epilogue.  Covers both epilogue forms (LDS walk of the one-block-per-tile kernels, side buffer of the persistent ones)."""
-    import re
     from dupl_amd import ops
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, "dupl_amd", "csrc", "common.h")).read()
-    body = src[src.index("constexpr float GELU_CLAMP"):src.index("float gelu_f(float x)")]
-    nums = [float(v) for v in re.findall(r"(-?\d+\.\d+(?:e-?\d+)?)f", body)]
-    clamp, coef = nums[0], nums[1:10]
+    import gemm32_ref as R32
+    clamp, coef = R32.gelu_coefficients()
     f32 = np.float32
 
     def phi(x):
-        u = np.minimum(np.abs(x), f32(clamp)).astype(f32)
-        q = np.full_like(u, f32(coef[0]))
-        for c in coef[1:]:
-            q = (q.astype(np.float64) * u + f32(c)).astype(f32)
-        he = (f32(0.5) * np.exp2(-(q * u).astype(f32).astype(np.float64)).astype(f32)).astype(f32)
-        return np.where(x >= 0, (f32(1.0) - he).astype(f32), he)
+        return R32.gelu_phi32(x, clamp, coef)
     g = torch.Generator().manual_seed(5)
     M, N, K = 1000, 768, 256
     x = (torch.randn(M, K, generator=g) * 1.5).to(dev)
@@ -1393,9 +1384,7 @@ def test_gelu_epilogues_follow_the_header_formula(dev):
     dx_lin, _ = ops.linear16(dy16.rows_slice(0, tokens), W16, alpha=alpha, b_kmajor=True)
     dx, _ = ops.linear16(dy16.rows_slice(0, tokens), W16, alpha=alpha, dgelu_of=pre2, b_kmajor=True)
     p2 = pre2.cpu().numpy()
-    e = ((f32(-0.72134752044448170368) * p2).astype(f32) * p2).astype(f32)
-    pdf = (f32(0.39894228040143267794) * np.exp2(e.astype(np.float64)).astype(f32)).astype(f32)
-    grad = (p2.astype(np.float64) * pdf + phi(p2)).astype(f32)                  # fmaf(x, pdf, Phi)
+    grad = R32.gelu_grad32(p2, clamp, coef)                                     # fmaf(x, pdf, Phi)
     lin = dx_lin.cpu().numpy()
     want = (lin * grad).astype(f32)
     err = np.abs(dx.cpu().numpy().astype(np.float64) - want.astype(np.float64))

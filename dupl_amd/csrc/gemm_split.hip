@@ -817,6 +817,11 @@ struct TileOrder {
     __device__ __forceinline__ bool has_tile(const int bid) const { return (bid >> 3) < q8 + ((bid & 7) < r8 ? 1 : 0); }
 };
 
+// k-steps every piece of work of the persistent kernels must have: their prologue fills the three LDS stages before it looks at the
+// piece's length.  The stream-K cuts and slices of the kernels keep to it, and so does the host where it checks K and chooses a
+// slice count.
+constexpr int G16_PROLOGUE = 3;
+
 // One 1 KB piece of a k-contiguous operand plane -> LDS by direct-to-LDS DMA; the source steps to the next k-tile.
 __device__ __forceinline__ void g16_dma_piece(const char*& gp, char* dst) {
     if (!(G16_ABL & 1))
@@ -1468,6 +1473,7 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(c
     constexpr int NMF = G::NMF, NR = G::NR;
     constexpr int SIDE = NW * 2048;
     static_assert(STAGES * STAGE + SIDE <= 160 * 1024, "LDS");
+    static_assert(STAGES <= G16_PROLOGUE, "the prologue fills every stage before it looks at the piece's length");
     __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE + SIDE];
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1526,8 +1532,8 @@ __global__ __launch_bounds__(64 * NWM * NWN, WPS) void gemm_f16x3_pring_kernel(c
         auto cut = [&](const int l) {
             int x = (int)((long)T * l / G);
             const int r = x % ntf;
-            if (r && r < 3) x -= r;
-            else if (r > ntf - 3) x += ntf - r;
+            if (r && r < G16_PROLOGUE) x -= r;
+            else if (r > ntf - G16_PROLOGUE) x += ntf - r;
             return x;
         };
         pos = cut(L);
@@ -1680,6 +1686,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
     constexpr int SIDE = NW * 2048;
     static_assert((2 * PA) % NW == 0, "pieces must divide over the waves, operand by operand");
     static_assert(STAGES * STAGE + SIDE <= 160 * 1024, "LDS");
+    static_assert(STAGES <= G16_PROLOGUE, "the prologue fills every stage before it looks at the piece's length");
     static_assert(1024 % RBA == 0 && 1024 % RBB == 0, "whole k-rows per DMA piece");
     static_assert(!SK || ACC == 1, "stream-K pieces meet in atomics");
     __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE + SIDE];
@@ -1858,7 +1865,7 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
             const int slice = u / nblk, lid = u - slice * nblk;
             const int per = (ntf + S - 1) / S;
             const int k0 = slice * per;
-            nt = min(per, ntf - k0);            // >= 3 for every slice (host)
+            nt = min(per, ntf - k0);            // >= G16_PROLOGUE for every slice (host)
             pos = lid * ntf + k0;
             pend = pos + nt;
             order.lid_origin(lid, m0, n0);
@@ -1868,8 +1875,8 @@ __device__ __forceinline__ void gemm_f16x3_km_body(const dupl_gemm16_desc& p, co
         auto cut = [&](const int l) {
             int x = (int)((long)T * l / G);
             const int r = x % ntf;
-            if (r && r < 3) x -= r;
-            else if (r > ntf - 3) x += ntf - r;
+            if (r && r < G16_PROLOGUE) x -= r;
+            else if (r > ntf - G16_PROLOGUE) x += ntf - r;
             return x;
         };
         pos = cut(L);
@@ -2015,6 +2022,7 @@ __device__ __forceinline__ void gemm_f16x3_km16_body(const dupl_gemm16_desc& p, 
     static_assert(RB == 4 && CB == 4, "wave tile 64 x 64: two phases of two row blocks, the 4 x 4 side-buffer epilogue");
     static_assert((2 * PA) % NW == 0, "pieces must divide over the waves, operand by operand");
     static_assert(STAGES * STAGE + SIDE <= 160 * 1024, "LDS");
+    static_assert(STAGES <= G16_PROLOGUE, "the prologue fills every stage before it looks at the piece's length");
     static_assert(!SK || ACC == 1, "stream-K pieces meet in atomics");
     __shared__ __attribute__((aligned(1024))) char smem[STAGES * STAGE + SIDE];
     const int tid = threadIdx.x;
@@ -2216,7 +2224,7 @@ __device__ __forceinline__ void gemm_f16x3_km16_body(const dupl_gemm16_desc& p, 
             const int slice = u / nblk, lid = u - slice * nblk;
             const int per = (ntf + S - 1) / S;
             const int k0 = slice * per;
-            nt = min(per, ntf - k0);            // >= 3 for every slice (host)
+            nt = min(per, ntf - k0);            // >= G16_PROLOGUE for every slice (host)
             pos = lid * ntf + k0;
             pend = pos + nt;
             order.lid_origin(lid, m0, n0);
@@ -2226,8 +2234,8 @@ __device__ __forceinline__ void gemm_f16x3_km16_body(const dupl_gemm16_desc& p, 
             auto cut = [&](const int l) {
                 int x = (int)((long)T * l / G);
                 const int r = x % ntf;
-                if (r && r < 3) x -= r;
-                else if (r > ntf - 3) x += ntf - r;
+                if (r && r < G16_PROLOGUE) x -= r;
+                else if (r > ntf - G16_PROLOGUE) x += ntf - r;
                 return x;
             };
             pos = cut(L);
@@ -2365,6 +2373,45 @@ constexpr int G16_GROUP_RING = 2;   // row tiles (256 rows) per group of the rin
                                     // XCD's L2 while it sweeps the columns (2 / 3: 320, 4: 312, 8: 304, 16: 285 TF/s-eq on 15696 x 3072 x 768)
 constexpr int G16_F1_BIG_FROM = 96; // format 1: 256 x 256 tiles from this many of them
 
+// dupl_gemm16_desc.tile: the codes dupl_gemm_f16x3 accepts
+constexpr int G16_TILES[] = {
+    0,    // the launcher's choice
+    3,    // gemm_f16x3_kernel, 128 x 64 on 4 waves; format 0, split-K
+    5,    // gemm_f16x3_kernel, 128 x 128 on 8 waves; format 0, split-K
+    6,    // gemm_f16x3_ring_kernel, 256 x 128 on 8 waves; format 0, one block per tile
+    7,    // gemm_f16x3_ring_kernel, 256 x 128 on 4 waves; format 0, one block per tile
+    8,    // gemm_f16x3_ring_kernel SINGLE, 256 x 256 on 8 waves; format 1, one block per tile
+    10,   // gemm_f16x3_pring_kernel, 256 x 128; format 0, persistent
+    11,   // gemm_f16x3_pring_kernel SK, 256 x 128; format 0, stream-K for DUPL_GEMM_ACCUM
+    12,   // gemm_f16x3_ring_kernel SINGLE, 256 x 128; format 1, one block per tile
+    14,   // gemm_f16x3_pring_kernel SINGLE, 256 x 128; format 1, persistent
+    18,   // gemm_f16x3_ring16_kernel, 256 x 256; format 1 on the 16x16x32 MFMA, one block per tile
+    22,   // gemm_f16x3_ring16_kernel, 256 x 128; format 1 on the 16x16x32 MFMA, one block per tile
+    24,   // k-major launches (single and grouped): gemm_f16x3_km_body, the 32x32x16 MFMA; any other launch: as 0
+    26,   // k-major launches (single and grouped): gemm_f16x3_km16_body, the 16x16x32 MFMA; any other launch: as 0
+    28,   // as 18 with the generic epilogue walk forced (EPI_GENERIC): the A/B partner of the epilogue forms
+    30,   // as 22 with the generic epilogue walk forced
+    32,   // as 26 with the generic epilogue walk forced
+};
+// A code resolved, once, into what it asks for
+struct g16_tile_t {
+    int family;     // the kernel of a k-contiguous launch (3 .. 22 above); 0 = the launcher's choice.  k-major launches do not look at it
+    bool forms;     // false: the generic epilogue walk forced
+    int km_body;    // the MFMA body of a k-major launch, 16 or 32; 0 = the launcher's choice per instantiation (KM16_* below)
+};
+static g16_tile_t g16_resolve_tile(const int code) {
+    switch (code) {
+        case 24: return {0, true, 32};
+        case 26: return {0, true, 16};
+        case 28: return {18, false, 0};
+        case 30: return {22, false, 0};
+        case 32: return {0, false, 16};
+        default: return {code, true, 0};
+    }
+}
+// all kernels of dupl_gemm_f16x3 share one signature: a choice of kernel is a pointer
+using g16_kernel_t = void (*)(dupl_gemm16_desc, int);
+
 // The k-major launches' automatic choice of the body (dupl_gemm16_desc.tile 0): per instantiation, the 16x16x32 body only where the
 // stand-alone A/B on the step's own shapes shows it faster (profiles/kmajor16_bodies.txt).  The whole-tile weight gradients (single
 // launch in deterministic mode, grouped launch) switch together: they carry the same bits.
@@ -2373,7 +2420,18 @@ constexpr bool KM16_DGRAD_EPI = true;       // data gradient, full epilogue: 314
 constexpr bool KM16_DGRAD_SK = true;        // stream-K data gradient: 3140 x 768 x 3072 60.2 -> 56.6 / 102.4 -> 93.1; 3140 x 768 x 2304 51.2 -> 48.5 / 82.4 -> 76.4
 constexpr bool KM16_WGRAD_SK = false;       // stream-K weight gradient: not in the step, not measured -- stays on the 32x32x16 body
 constexpr bool KM16_WGRAD_TILE = true;      // whole-tile weight gradients: a block's four at K = 3168, grouped, 121.7 -> 112.5 / 239.8 -> 224.9
-static bool g16_km16(const int tile, const bool automatic) { return tile == 26 || tile == 32 || (tile != 24 && automatic); }
+static bool g16_km16(const g16_tile_t& t, const bool automatic) { return t.km_body ? t.km_body == 16 : automatic; }
+// The k-major kernels (256 x 128, persistent, 3 stages) by body and epilogue form; the forms exist for the full-epilogue data gradient on
+// the 16x16x32 body only
+template <bool SK, int ACC, bool AKM, bool BKM>
+static g16_kernel_t g16_km_kernel(const bool km16, const int epi = EPI_GENERIC) {
+    if (!km16) return gemm_f16x3_km_kernel<2, 2, 4, 2, 2, SK, ACC, AKM, BKM, 3, 32>;
+    if constexpr (!SK && ACC == 0) {
+        if (epi == EPI_D) return gemm_f16x3_km_kernel<2, 2, 4, 2, 2, SK, ACC, AKM, BKM, 3, 16, EPI_D>;
+        if (epi == EPI_A) return gemm_f16x3_km_kernel<2, 2, 4, 2, 2, SK, ACC, AKM, BKM, 3, 16, EPI_A>;
+    }
+    return gemm_f16x3_km_kernel<2, 2, 4, 2, 2, SK, ACC, AKM, BKM, 3, 16>;
+}
 
 // The epilogue forms (EPI_*): the launcher matches flags, pointers and c_rows of a descriptor against the forms the step launches and takes
 // the specialised instantiation where the stand-alone A/B on the step's own shapes shows it faster or equal (tools/gemm16_bench with
@@ -2437,7 +2495,7 @@ static bool g16_operands_ok(const dupl_gemm16_desc& d) {
     if (d.a_layout < 0 || d.a_layout > 1 || d.b_layout < 0 || d.b_layout > 1 || d.ka_valid < 0 || d.kb_valid < 0) return false;
     if (d.a_layout || d.b_layout) {
         // k-major operand(s): format 1 planes, the 3-stage prologue, whole 16-byte chunks of rows, k_valid of a k-major operand only
-        if (d.fmt != 1 || d.K / TBK < 3) return false;
+        if (d.fmt != 1 || d.K / TBK < G16_PROLOGUE) return false;
         if ((d.a_layout && (d.M & 7)) || (d.b_layout && (d.N & 7))) return false;
         if (d.ka_valid > d.K || d.kb_valid > d.K) return false;
         if ((!d.a_layout && d.ka_valid) || (!d.b_layout && d.kb_valid)) return false;
@@ -2466,10 +2524,9 @@ extern "C" int dupl_gemm_f16x3_group(const dupl_gemm16_desc* descs, int32_t n, d
     }
     g.first[n] = total;
     const dim3 grid((unsigned)(8 * ((total + 7) / 8)));
-    if (g16_km16(tile, KM16_WGRAD_TILE))
-        DUPL_LAUNCH((gemm_f16x3_km_group_kernel<2, 2, 4, 2, 2, 16>), grid, dim3(512), 0, (hipStream_t)stream, g, group ? group : G16_GROUP_RING);
-    else
-        DUPL_LAUNCH((gemm_f16x3_km_group_kernel<2, 2, 4, 2, 2, 32>), grid, dim3(512), 0, (hipStream_t)stream, g, group ? group : G16_GROUP_RING);
+    void (*const kernel)(g16_group_args, int) = g16_km16(g16_resolve_tile(tile), KM16_WGRAD_TILE) ? gemm_f16x3_km_group_kernel<2, 2, 4, 2, 2, 16>
+                                                                                                  : gemm_f16x3_km_group_kernel<2, 2, 4, 2, 2, 32>;
+    DUPL_LAUNCH(kernel, grid, dim3(512), 0, (hipStream_t)stream, g, group ? group : G16_GROUP_RING);
     return dupl_launch_status();
 }
 
@@ -2493,25 +2550,56 @@ static bool g16_split_rows(const dupl_gemm16_desc& d, const int M1, dupl_gemm16_
     return d2.C || d2.C_hi;
 }
 
-// dupl_gemm16_desc.tile: the codes dupl_gemm_f16x3 accepts
-constexpr int G16_TILES[] = {
-    0,    // the launcher's choice
-    3,    // gemm_f16x3_kernel, 128 x 64 on 4 waves; format 0, split-K
-    5,    // gemm_f16x3_kernel, 128 x 128 on 8 waves; format 0, split-K
-    6,    // gemm_f16x3_ring_kernel, 256 x 128 on 8 waves; format 0, one block per tile
-    7,    // gemm_f16x3_ring_kernel, 256 x 128 on 4 waves; format 0, one block per tile
-    8,    // gemm_f16x3_ring_kernel SINGLE, 256 x 256 on 8 waves; format 1, one block per tile
-    10,   // gemm_f16x3_pring_kernel, 256 x 128; format 0, persistent
-    11,   // gemm_f16x3_pring_kernel SK, 256 x 128; format 0, stream-K for DUPL_GEMM_ACCUM
-    12,   // gemm_f16x3_ring_kernel SINGLE, 256 x 128; format 1, one block per tile
-    14,   // gemm_f16x3_pring_kernel SINGLE, 256 x 128; format 1, persistent
-    18,   // gemm_f16x3_ring16_kernel, 256 x 256; format 1 on the 16x16x32 MFMA, one block per tile
-    22,   // gemm_f16x3_ring16_kernel, 256 x 128; format 1 on the 16x16x32 MFMA, one block per tile
-    24,   // k-major launches (single and grouped): gemm_f16x3_km_body, the 32x32x16 MFMA; any other launch: as 0
-    26,   // k-major launches (single and grouped): gemm_f16x3_km16_body, the 16x16x32 MFMA; any other launch: as 0
-    28,   // as 18 with the generic epilogue walk forced (EPI_GENERIC): the A/B partner of the epilogue forms
-    30,   // as 22 with the generic epilogue walk forced
-    32,   // as 26 with the generic epilogue walk forced
+// ---- dupl_gemm_f16x3 in three steps: g16_check (every refusal), g16_choose (what to launch, as values), and one place that launches.
+
+// 1. Every condition under which dupl_gemm_f16x3 returns DUPL_ERR_ARG.  d: with the stand-in lo planes of products = 1 (`single`).
+static bool g16_check(const dupl_gemm16_desc& d, const bool single) {
+    if (!g16_operands_ok(d)) return false;
+    if (d.products != 0 && d.products != 1 && d.products != 3) return false;      // 0 = 3: the f16x3 kernels
+    if (d.concurrency < 0 || d.concurrency > 8 || d.persist_blocks < 0 || d.persist_blocks > 1024 || (d.persist_blocks & 7)) return false;
+    bool known_tile = false;
+    for (const int t : G16_TILES) known_tile |= d.tile == t;
+    if (!known_tile) return false;
+    if (!d.C && !d.C_hi) return false;
+    if ((d.C_hi == nullptr) != (d.C_lo == nullptr)) return false;
+    if ((d.flags & (DUPL_GEMM_STORE_PRE | DUPL_GEMM_MUL_DGELU | DUPL_GEMM_MUL_RELUMASK)) && !d.aux) return false;
+    if (d.flags & ~(DUPL_GEMM_GELU | DUPL_GEMM_RELU | DUPL_GEMM_STORE_PRE | DUPL_GEMM_ACCUM | DUPL_GEMM_MUL_DGELU | DUPL_GEMM_MUL_RELUMASK))
+        return false;
+    const bool kmajor = d.a_layout || d.b_layout, accum = d.flags & DUPL_GEMM_ACCUM;
+    if (accum && (!d.C || d.C_hi || d.bias || d.res || d.c_rows)) return false;   // C += alpha * A B^T, nothing else
+    if (d.c_rows < 0 || (d.c_rows && (d.flags & (DUPL_GEMM_MUL_DGELU | DUPL_GEMM_MUL_RELUMASK)))) return false;
+    if (d.amax_out && (accum || d.c_rows || (reinterpret_cast<uintptr_t>(d.amax_out) & 3))) return false;
+    if (d.fmt < 0 || d.fmt > 1 || d.out_exp < 0 || d.out_exp > 15 || (d.out_exp && d.fmt != 1) || (d.fmt == 1 && !kmajor && (accum || d.amax_out)))
+        return false;
+    if (single && (accum || kmajor)) return false;      // products = 1 is the forward only: k-contiguous operands, C = ...
+    if (kmajor) {
+        // the three k-major forms: the data gradient with the full epilogue (dy k-contiguous, W k-major); the data gradient with a LINEAR
+        // epilogue into a zero-filled dx, stream-K (in deterministic mode the caller takes the one-block-per-tile form instead); the
+        // weight gradient (both operands token-major)
+        if (!accum && (d.a_layout || !d.b_layout)) return false;
+        if (accum && !d.a_layout && (!d.b_layout || d.deterministic)) return false;
+        if (accum && d.a_layout && !d.b_layout) return false;
+    }
+    return true;
+}
+
+// 2. What to launch: at most two launches on the stream (the row split of the forward).  A launch passes the caller's descriptor or one of
+// the plan's own (`own`: the stream-K descriptor with its slice count resolved, the two parts of a row split).
+struct g16_launch_t {
+    g16_kernel_t kernel;
+    dim3 grid, block;
+    int group;                            // the kernels' second argument: row tiles per group of the block -> tile order
+    const dupl_gemm16_desc* d;
+};
+struct g16_plan {
+    int n = 0;
+    g16_launch_t l[2];
+    dupl_gemm16_desc own[2];
+    void add(const g16_kernel_t kernel, const dim3 grid, const dim3 block, const int group, const dupl_gemm16_desc* d) {
+        l[n++] = g16_launch_t{kernel, grid, block, group, d};
+    }
+    g16_plan() = default;
+    g16_plan(const g16_plan&) = delete;   // (l[].d may point into own)
 };
 
 // The two forward tiles on the 16x16x32 MFMA (gemm_f16x3_ring16_kernel), for the format 1 f16x3 forward and the single-product forward
@@ -2519,19 +2607,17 @@ constexpr int G16_TILES[] = {
 static int g16_tile16(const dupl_gemm16_desc& d) {
     return ((d.M + 255) / 256) * ((d.N + 255) / 256) >= G16_F1_BIG_FROM ? 18 : 22;
 }
-using g16_kernel_t = void (*)(dupl_gemm16_desc, int);
 // big / small: the instantiations of the two tiles by epilogue form ([EPI_GENERIC] .. [EPI_R]; NULL = that form has none); forms: take
 // them (the form is matched per launch: the two parts of a row split may differ)
 constexpr int EPI_FWD_COUNT = 4;        // forms of the forward kernel, generic included: what g16_epi_form may return
 static_assert(EPI_GENERIC == 0 && EPI_P < EPI_FWD_COUNT && EPI_G < EPI_FWD_COUNT && EPI_R < EPI_FWD_COUNT, "the forward form tables are indexed by EPI_*");
-static void g16_launch16(const dupl_gemm16_desc& d, const int t, const bool automatic, const int group, hipStream_t s,
+static void g16_choose16(g16_plan& pl, const dupl_gemm16_desc& d, const int t, const bool automatic, const int group,
                          const g16_kernel_t (&big)[EPI_FWD_COUNT], const g16_kernel_t (&small)[EPI_FWD_COUNT], const bool forms) {
-    auto launch = [&](const g16_kernel_t (&ks)[EPI_FWD_COUNT], const dupl_gemm16_desc& q, const int bn) {
+    auto add = [&](const g16_kernel_t (&ks)[EPI_FWD_COUNT], const dupl_gemm16_desc& q, const int bn) {
         const int f = forms ? g16_epi_form(q) : EPI_GENERIC;
-        const g16_kernel_t k = ks[f] ? ks[f] : ks[EPI_GENERIC];
-        DUPL_LAUNCH(k, dim3((unsigned)(((q.M + 255) / 256) * ((q.N + bn - 1) / bn))), dim3(512), 0, s, q, group);
+        pl.add(ks[f] ? ks[f] : ks[EPI_GENERIC], dim3((unsigned)(((q.M + 255) / 256) * ((q.N + bn - 1) / bn))), dim3(512), group, &q);
     };
-    if (t == 22) return launch(small, d, 128);
+    if (t == 22) return add(small, d, 128);
     // One block per CU and launch: nb22 tiles take ceil(nb22 / 256) rounds, and a last round that holds a few tiles costs as
     // much as a full one.  The merged ms-CAM / training pass of a step is exactly that case -- 21 976 rows = 86 row tiles, x
     // {12, 9, 3} column tiles = 1 032 / 774 / 258 tiles = 4, 3, 1 full rounds + 8 / 6 / 2 tiles (rocprofv3, one stream: 340 us
@@ -2542,15 +2628,146 @@ static void g16_launch16(const dupl_gemm16_desc& d, const int t, const bool auto
     const int cn = (d.N + 255) / 256, rm = (d.M + 255) / 256, cus = 256;
     const int nb22 = rm * cn, full = nb22 / cus, tail = nb22 - full * cus;
     const int r_big = full > 0 ? (full * cus) / cn : 0;
-    dupl_gemm16_desc d1, d2;
-    if (automatic && full > 0 && tail > 0 && tail * 10 < cus * 3 && r_big > 0 && r_big < rm && !d.amax_out && g16_split_rows(d, r_big * 256, d1, d2)) {
-        launch(big, d1, 256);
-        launch(small, d2, 128);
-    } else launch(big, d, 256);
+    if (automatic && full > 0 && tail > 0 && tail * 10 < cus * 3 && r_big > 0 && r_big < rm && !d.amax_out &&
+        g16_split_rows(d, r_big * 256, pl.own[0], pl.own[1])) {
+        add(big, pl.own[0], 256);
+        add(small, pl.own[1], 128);
+    } else add(big, d, 256);
 }
 
-static int g16_launch_hi(const dupl_gemm16_desc& d, const int tile, const int group, hipStream_t s);      // (below: its kernels are emitted last)
+// products = 1: the single-product forward, gemm_f16x3_ring16_kernel<.., NP = 1> on the tiles and with the row split of the format 1
+// forward (g16_choose16).
+#ifndef G16H_STAGES
+#define G16H_STAGES 4   // ring depth of both tiles (4 x 32 KB / 4 x 24 KB)
+#endif
+static void g16_choose_hi(g16_plan& pl, const dupl_gemm16_desc& d, const g16_tile_t& t, const int group);      // (below: its kernels are emitted last)
 
+// The k-major launches: the backward GEMMs on the forward's own planes (gemm_f16x3_km_kernel; 256 x 128, persistent).  whole: the grid
+// of the forms in which a block owns whole tiles; sk: the weight gradient may split K.
+static void g16_choose_km(g16_plan& pl, const dupl_gemm16_desc& d, const g16_tile_t& t, const bool sk, const int persist_blocks, const dim3 whole,
+                          const int group) {
+    const bool accum = d.flags & DUPL_GEMM_ACCUM;
+    const int nb21 = ((d.M + 255) / 256) * ((d.N + 127) / 128);
+    const dim3 block(512), all((unsigned)persist_blocks);
+    if (!accum) {      // the data gradient with the full epilogue
+        const bool km16 = g16_km16(t, KM16_DGRAD_EPI);
+        return pl.add(g16_km_kernel<false, 0, false, true>(km16, t.forms ? g16_epi_form_km(d) : EPI_GENERIC), whole, block, group, &d);
+    }
+    // stream-K forms: aligned k-slices (dupl_gemm16_desc.sk_slices: 0 = as many slices per tile as the grid has blocks for, every
+    // slice >= G16_PROLOGUE k-steps; < 0 = the equal-run cut of round 4)
+    dupl_gemm16_desc& dsk = pl.own[0];
+    dsk = d;
+    const int ntf = d.K / TBK;
+    auto per = [&](int s_) { return (ntf + s_ - 1) / s_; };
+    auto fits = [&](int s_) {
+        return s_ > 0 && (long)nb21 * s_ <= persist_blocks && per(s_) >= G16_PROLOGUE && ntf - (s_ - 1) * per(s_) >= G16_PROLOGUE;
+    };
+    // an explicit slice count that does not fit THIS shape (more units than blocks, a slice shorter than the prologue) falls back
+    // to the library's choice instead of failing the launch: the value is a per-model tuning default that meets every shape of
+    // the step, including the launches that never look at it (deterministic mode, one block per tile) -- ADVICE r5
+    if (dsk.sk_slices > 0 && !fits(dsk.sk_slices)) dsk.sk_slices = 0;
+    if (dsk.sk_slices == 0) {
+        // more tiles than blocks: the equal-run cut (a block's run then spans several tiles); otherwise as many slices as
+        // there are blocks for.  Measured (profiles/r05_sk_slices.txt): stand-alone 3140 x 768 x 3072 244 vs 211 TF/s-eq, 1570 x
+        // 768 x 3072 171-187 vs 149; with a second stream's launch in flight the 4-image shape is slower stand-alone (2 slices
+        // = 156 of 192 blocks: 287 vs 312) but the STEP is faster with it at 4 images too (52.0 vs 52.35 ms, 30.5 vs 30.9 at 2):
+        // the blocks it leaves free and the fabric bandwidth it no longer takes go to the other student's kernels
+        int S = nb21 > persist_blocks ? -1 : persist_blocks / nb21;
+        while (S > 1 && (per(S) < G16_PROLOGUE || ntf - (S - 1) * per(S) < G16_PROLOGUE)) --S;
+        dsk.sk_slices = S;
+    }
+    if (dsk.sk_slices > 0 && !fits(dsk.sk_slices)) dsk.sk_slices = -1;      // (cannot happen for the choice above: kept as a guard -> equal runs)
+    if (!d.a_layout)
+        // a data gradient with a LINEAR epilogue (dx = alpha dy . W, nothing else) into a zero-filled dx: stream-K pieces meet in
+        // fp32 atomics, so that the N = 768 outputs (78 tiles of 256 x 128 at 4 images, 42 at 2) run on every CU
+        pl.add(g16_km_kernel<true, 1, false, true>(g16_km16(t, KM16_DGRAD_SK)), all, block, group, &dsk);
+    else if (sk) pl.add(g16_km_kernel<true, 1, true, true>(g16_km16(t, KM16_WGRAD_SK)), all, block, group, &dsk);
+    else pl.add(g16_km_kernel<false, 2, true, true>(g16_km16(t, KM16_WGRAD_TILE)), whole, block, group, &d);
+}
+
+static void g16_choose(g16_plan& pl, const dupl_gemm16_desc& d, const bool single) {
+    const g16_tile_t t = g16_resolve_tile(d.tile);
+    const bool kmajor = d.a_layout || d.b_layout, accum = d.flags & DUPL_GEMM_ACCUM;
+    const int concurrency = d.concurrency > 0 ? d.concurrency : 1;
+    const int persist_blocks = d.persist_blocks ? d.persist_blocks : (concurrency >= 2 ? 192 : 256);
+    const int group_m = d.group ? d.group : G16_GROUP_M, group_ring = d.group ? d.group : G16_GROUP_RING;
+    const int ntf = d.K / TBK, nb21 = ((d.M + 255) / 256) * ((d.N + 127) / 128);
+    if (single) return g16_choose_hi(pl, d, t, group_ring);
+    // split-K for accumulating GEMMs (weight gradients: few output tiles, K = all tokens): >= ~2 blocks per CU,
+    // >= 8 k-tiles per split
+    int ksplit = 1;
+    if (accum) {
+        const long tiles = (long)((d.M + 127) / 128) * ((d.N + 127) / 128);
+        ksplit = (int)((512 + tiles - 1) / tiles);
+        const int maxs = (ntf + 7) / 8;
+        if (ksplit > maxs) ksplit = maxs;
+        if (ksplit < 1) ksplit = 1;
+        if (d.deterministic) ksplit = 1;      // no fp32 atomics
+    }
+    auto blocks = [&](int bm, int bn) { return dim3((unsigned)(((d.M + bm - 1) / bm) * ((d.N + bn - 1) / bn)), (unsigned)ksplit); };
+    // grid of a persistent kernel, every block walks the same number of tiles: with tx tiles per XCD and at most maxb / 8 blocks per
+    // XCD the walk takes rounds = ceil(tx / (maxb / 8)) tiles, and ceil(tx / rounds) blocks per XCD are enough for that -- 600 tiles
+    // run as 3 x 200 instead of 2.3 x 256 (the kernel is power-bound: a few CUs less cost nothing, an idle last round does)
+    auto persist_grid = [&](const int nblk) {
+        const int tx = (nblk + 7) / 8, bmax = persist_blocks / 8;
+        const int rounds = (tx + bmax - 1) / bmax;
+        return dim3((unsigned)(8 * ((tx + rounds - 1) / rounds)));
+    };
+    if (kmajor) return g16_choose_km(pl, d, t, accum && !d.deterministic && ksplit > 1, persist_blocks, persist_grid(nb21), group_ring);
+    if (d.fmt == 1) {
+        // format 1 operands: one accumulator set.  256 x 256 on 8 waves (wave tile 128 x 64, two LDS stages of 64 KB; tile 8) where
+        // the grid fills the chip, 256 x 128 (the ring kernel's tile with half the accumulators; 12) below.  One block per tile: the
+        // persistent form of 256 x 128 (14) measures the same or 1-3 % less, that of 256 x 256 spills (228 vs 353 TF/s-eq)
+        // (round 6, measured and dropped: the same 256 x 256 tile on FOUR waves of 128 x 128 -- one wave per SIMD in the 512-register
+        // file, 252 VGPRs + 256 accumulation registers, no spill, 16 instead of 24 fragment reads per 48 MFMAs -- is 8-20 % SLOWER on
+        // every forward shape, alone and next to a second stream (15 696 x 3 072 x 768 bias + GELU -> planes: 247 vs 300 TF/s-eq,
+        // 15 696 x 768 x 3 072 bias + residual: 295 vs 328; profiles/r06_tile16.txt): with one wave per SIMD nothing covers a wave's
+        // own waits, the result tile 7 gave in round 3)
+        // (18 / 22: the same two tiles on the 16x16x32 MFMA, gemm_f16x3_ring16_kernel; the launcher's own choice, since the clock the
+        // chip holds under this loop is higher on that shape.  Both tiles switch together: they are bit-identical to each other)
+        int f = (t.family == 8 || t.family == 12 || t.family == 14 || t.family == 18 || t.family == 22) ? t.family : g16_tile16(d);
+        if (ntf < G16_PROLOGUE && f == 14) f = 12;
+        if (f == 18 || f == 22) {
+            static const g16_kernel_t big[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>, gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_P>,
+                                                gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_G>, gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_R>};
+            static const g16_kernel_t small[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>, gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_P>,
+                                                  gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_G>, gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_R>};
+            return g16_choose16(pl, d, f, t.family == 0, group_ring, big, small, t.forms);
+        }
+        if (f == 8) return pl.add(gemm_f16x3_ring_kernel<4, 2, 2, 4, 2, 2, true>, blocks(256, 256), dim3(512), group_ring, &d);
+        if (f == 12) return pl.add(gemm_f16x3_ring_kernel<2, 2, 4, 2, 2, 3, true>, blocks(256, 128), dim3(512), group_ring, &d);
+        return pl.add(gemm_f16x3_pring_kernel<2, 2, 4, 2, 2, false, true, 3>, persist_grid(nb21), dim3(512), group_ring, &d);
+    }
+    // format 0 operands
+    int f = t.family;
+    if (f == 0) {
+        // Measured on the shapes of the step (tools/gemm16_bench -w 200 with and without -2, profiles/r03_gemm16_tiles.txt),
+        // sustained clocks.  The persistent 256 x 128 ring kernel (tile 10; 6 = the same, one block per tile) is one block
+        // per CU: it wins wherever its grid covers a good part of the chip -- >= 64 tiles when a second stream feeds the chip
+        // as well (the two students: dupl_gemm16_desc.concurrency 2), >= 128 tiles alone.  The weight gradients go to its
+        // stream-K form (tile 11) when every block gets >= 10 k-steps (K = 1600, one stream: 3072 x 768 143 vs 117, 2304 x 768 116 vs 100): 3072 x 768 x 3168 alone 155 -> 205 TF/s-eq, with a
+        // second stream 219 -> 238 (there only from 64 tiles on: 2304 x 768 loses 6 % to two co-resident 128 x 128 blocks of
+        // both streams); the rest stay on split-K grids of 128 x 128 (tile 5, two blocks per CU) / 128 x 64 (tile 3).
+        const long b256 = nb21;
+        const long b128 = (long)((d.M + 127) / 128) * ((d.N + 127) / 128) * ksplit;
+        const bool ring = b256 >= (concurrency >= 2 ? 64 : 128);
+        if (!accum && ring) f = 10;
+        else if (accum && ksplit > 1 && ntf >= 8 && b256 * ntf >= 10L * persist_blocks && (concurrency < 2 || b256 >= 64)) f = 11;
+        else f = b128 < 200 ? 3 : 5;
+    }
+    if (f == 10 && (accum || ntf < G16_PROLOGUE)) f = 6;      // the persistent kernel has no split-K and a 3-stage prologue
+    if (f == 11 && (!accum || d.deterministic || ntf < 8)) f = accum ? 5 : 6;   // stream-K: atomics, pieces >= G16_PROLOGUE k-steps
+    // (11: the caller's descriptor as it is -- this kernel takes the equal-run cut whatever sk_slices says)
+    if (f == 11) return pl.add(gemm_f16x3_pring_kernel<2, 2, 4, 2, 2, true>, dim3((unsigned)persist_blocks), dim3(512), group_ring, &d);
+    if (f == 10) return pl.add(gemm_f16x3_pring_kernel<2, 2, 4, 2, 2>, persist_grid(nb21), dim3(512), group_ring, &d);
+    if (f == 8 || f == 12 || f == 14 || f == 18 || f == 22) f = 5;      // single-accumulator tiles: format 1 operands only (above)
+    if (f == 6) return pl.add(gemm_f16x3_ring_kernel<2, 2, 4, 2, 2>, blocks(256, 128), dim3(512), group_ring, &d);
+    if (f == 7) return pl.add(gemm_f16x3_ring_kernel<4, 2, 2, 2, 1>, blocks(256, 128), dim3(256), group_ring, &d);
+    if (f == 3) return pl.add(gemm_f16x3_kernel<2, 1, 2, 2, 2>, blocks(128, 64), dim3(256), group_m, &d);
+    pl.add(gemm_f16x3_kernel<2, 1, 2, 4, 4>, blocks(128, 128), dim3(512), group_m, &d);
+}
+
+// 3. Launch.
 extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) {
     if (!d) return DUPL_ERR_ARG;
     // products = 1 reads no lo plane: NULL lo pointers are accepted, and stand in as the hi planes for the checks both forms share
@@ -2562,195 +2779,17 @@ extern "C" int dupl_gemm_f16x3(const dupl_gemm16_desc* d, dupl_stream_t stream) 
         if (!hi1.B_lo) hi1.B_lo = hi1.B_hi;
         d = &hi1;
     }
-    if (!g16_operands_ok(*d)) return DUPL_ERR_ARG;
-    if (d->products != 0 && d->products != 1 && d->products != 3) return DUPL_ERR_ARG;      // 0 = 3: the f16x3 kernels
-    if (d->concurrency < 0 || d->concurrency > 8 || d->persist_blocks < 0 || d->persist_blocks > 1024 || (d->persist_blocks & 7))
-        return DUPL_ERR_ARG;
-    bool known_tile = false;
-    for (const int t : G16_TILES) known_tile |= d->tile == t;
-    if (!known_tile) return DUPL_ERR_ARG;
-    const bool kmajor = d->a_layout || d->b_layout;
-    // (the k-major bodies' codes mean nothing elsewhere; 28 / 30 are 18 / 22 with the generic epilogue forced, 32 is 26 with it)
-    const bool epi_forms = d->tile != 28 && d->tile != 30 && d->tile != 32;
-    const int tile_code = d->tile == 28 ? 18 : d->tile == 30 ? 22 : d->tile;
-    const int g16_tile = (tile_code == 24 || tile_code == 26 || tile_code == 32) && !kmajor ? 0 : tile_code;
-    const int g16_concurrency = d->concurrency > 0 ? d->concurrency : 1;
-    const int g16_persist_blocks = d->persist_blocks ? d->persist_blocks : (g16_concurrency >= 2 ? 192 : 256);
-    const int g16_group_m = d->group ? d->group : G16_GROUP_M, g16_group_ring = d->group ? d->group : G16_GROUP_RING;
-    if (!d->C && !d->C_hi) return DUPL_ERR_ARG;
-    if ((d->C_hi == nullptr) != (d->C_lo == nullptr)) return DUPL_ERR_ARG;
-    if ((d->flags & (DUPL_GEMM_STORE_PRE | DUPL_GEMM_MUL_DGELU | DUPL_GEMM_MUL_RELUMASK)) && !d->aux) return DUPL_ERR_ARG;
-    if (d->flags & ~(DUPL_GEMM_GELU | DUPL_GEMM_RELU | DUPL_GEMM_STORE_PRE | DUPL_GEMM_ACCUM | DUPL_GEMM_MUL_DGELU |
-                     DUPL_GEMM_MUL_RELUMASK))
-        return DUPL_ERR_ARG;
-    const bool accum = d->flags & DUPL_GEMM_ACCUM;
-    if (accum && (!d->C || d->C_hi || d->bias || d->res || d->c_rows)) return DUPL_ERR_ARG;   // C += alpha * A B^T, nothing else
-    if (d->c_rows < 0 || (d->c_rows && (d->flags & (DUPL_GEMM_MUL_DGELU | DUPL_GEMM_MUL_RELUMASK)))) return DUPL_ERR_ARG;
-    if (d->amax_out && (accum || d->c_rows || (reinterpret_cast<uintptr_t>(d->amax_out) & 3))) return DUPL_ERR_ARG;
-    if (d->fmt < 0 || d->fmt > 1 || d->out_exp < 0 || d->out_exp > 15 || (d->out_exp && d->fmt != 1) ||
-        (d->fmt == 1 && !kmajor && (accum || d->amax_out)))
-        return DUPL_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (single) {       // the forward only: k-contiguous operands, C = ...
-        if (accum || kmajor) return DUPL_ERR_ARG;
-        return g16_launch_hi(*d, g16_tile, g16_group_ring, s);
-    }
-    // split-K for accumulating GEMMs (weight gradients: few output tiles, K = all tokens): >= ~2 blocks per CU,
-    // >= 8 k-tiles per split
-    int ksplit = 1;
-    if (accum) {
-        const long tiles = (long)((d->M + 127) / 128) * ((d->N + 127) / 128);
-        ksplit = (int)((512 + tiles - 1) / tiles);
-        const int maxs = (d->K / TBK + 7) / 8;
-        if (ksplit > maxs) ksplit = maxs;
-        if (ksplit < 1) ksplit = 1;
-        if (d->deterministic) ksplit = 1;      // no fp32 atomics
-    }
-    int tile = g16_tile;
-    if (tile == 0) {
-        // Measured on the shapes of the step (tools/gemm16_bench -w 200 with and without -2, profiles/r03_gemm16_tiles.txt),
-        // sustained clocks.  The persistent 256 x 128 ring kernel (tile 10; 6 = the same, one block per tile) is one block
-        // per CU: it wins wherever its grid covers a good part of the chip -- >= 64 tiles when a second stream feeds the chip
-        // as well (the two students: dupl_gemm16_desc.concurrency 2), >= 128 tiles alone.  The weight gradients go to its
-        // stream-K form (tile 11) when every block gets >= 10 k-steps (K = 1600, one stream: 3072 x 768 143 vs 117, 2304 x 768 116 vs 100): 3072 x 768 x 3168 alone 155 -> 205 TF/s-eq, with a
-        // second stream 219 -> 238 (there only from 64 tiles on: 2304 x 768 loses 6 % to two co-resident 128 x 128 blocks of
-        // both streams); the rest stay on split-K grids of 128 x 128 (tile 5, two blocks per CU) / 128 x 64 (tile 3).
-        const long b256 = (long)((d->M + 255) / 256) * ((d->N + 127) / 128);
-        const long b128 = (long)((d->M + 127) / 128) * ((d->N + 127) / 128) * ksplit;
-        const bool ring = b256 >= (g16_concurrency >= 2 ? 64 : 128);
-        if (!accum && ring) tile = 10;
-        else if (accum && ksplit > 1 && d->K / TBK >= 8 && b256 * (d->K / TBK) >= 10L * g16_persist_blocks &&
-                 (g16_concurrency < 2 || b256 >= 64))
-            tile = 11;
-        else tile = b128 < 200 ? 3 : 5;
-    }
-    auto blocks = [&](int bm, int bn) { return dim3((unsigned)(((d->M + bm - 1) / bm) * ((d->N + bn - 1) / bn)), (unsigned)ksplit); };
-    // grid of a persistent kernel, every block walks the same number of tiles: with tx tiles per XCD and at most maxb / 8 blocks per
-    // XCD the walk takes rounds = ceil(tx / (maxb / 8)) tiles, and ceil(tx / rounds) blocks per XCD are enough for that -- 600 tiles
-    // run as 3 x 200 instead of 2.3 x 256 (the kernel is power-bound: a few CUs less cost nothing, an idle last round does)
-    auto persist_grid = [&](const int nblk) {
-        const int tx = (nblk + 7) / 8, bmax = g16_persist_blocks / 8;
-        const int rounds = (tx + bmax - 1) / bmax;
-        return dim3((unsigned)(8 * ((tx + rounds - 1) / rounds)));
-    };
-    if (kmajor) {
-        // k-major operand(s): the backward GEMMs on the forward's own planes (gemm_f16x3_km_kernel; 256 x 128, persistent)
-        const int nb21 = ((d->M + 255) / 256) * ((d->N + 127) / 128);
-        const bool sk = accum && !d->deterministic && ksplit > 1;
-        // stream-K forms: aligned k-slices (dupl_gemm16_desc.sk_slices: 0 = as many slices per tile as the grid has blocks for, every
-        // slice >= 3 k-steps (the prologue depth); < 0 = the equal-run cut of round 4)
-        dupl_gemm16_desc dsk = *d;
-        if (accum) {
-            const int ntf = d->K / TBK;
-            auto per = [&](int s_) { return (ntf + s_ - 1) / s_; };
-            auto fits = [&](int s_) { return s_ > 0 && (long)nb21 * s_ <= g16_persist_blocks && per(s_) >= 3 && ntf - (s_ - 1) * per(s_) >= 3; };
-            // an explicit slice count that does not fit THIS shape (more units than blocks, a slice shorter than the prologue) falls back
-            // to the library's choice instead of failing the launch: the value is a per-model tuning default that meets every shape of
-            // the step, including the launches that never look at it (deterministic mode, one block per tile) -- ADVICE r5
-            if (dsk.sk_slices > 0 && !fits(dsk.sk_slices)) dsk.sk_slices = 0;
-            if (dsk.sk_slices == 0) {
-                // more tiles than blocks: the equal-run cut (a block's run then spans several tiles); otherwise as many slices as
-                // there are blocks for.  Measured (profiles/r05_sk_slices.txt): stand-alone 3140 x 768 x 3072 244 vs 211 TF/s-eq, 1570 x
-                // 768 x 3072 171-187 vs 149; with a second stream's launch in flight the 4-image shape is slower stand-alone (2 slices
-                // = 156 of 192 blocks: 287 vs 312) but the STEP is faster with it at 4 images too (52.0 vs 52.35 ms, 30.5 vs 30.9 at 2):
-                // the blocks it leaves free and the fabric bandwidth it no longer takes go to the other student's kernels
-                int S = nb21 > g16_persist_blocks ? -1 : g16_persist_blocks / nb21;
-                while (S > 1 && (per(S) < 3 || ntf - (S - 1) * per(S) < 3)) --S;
-                dsk.sk_slices = S;
-            }
-            if (dsk.sk_slices > 0 && !fits(dsk.sk_slices)) dsk.sk_slices = -1;      // (cannot happen for the choice above: kept as a guard -> equal runs)
-        }
-        if (accum && !d->a_layout) {
-            // a data gradient with a LINEAR epilogue (dx = alpha dy . W, nothing else) into a zero-filled dx: stream-K pieces meet in
-            // fp32 atomics, so that the N = 768 outputs (78 tiles of 256 x 128 at 4 images, 42 at 2) run on every CU
-            if (!d->b_layout || d->deterministic) return DUPL_ERR_ARG;      // (the caller takes the one-block-per-tile form then)
-            if (g16_km16(g16_tile, KM16_DGRAD_SK))
-                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, false, true, 3, 16>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
-            else
-                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, false, true, 3, 32>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
-        } else if (accum) {
-            if (!(d->a_layout && d->b_layout)) return DUPL_ERR_ARG;            // the weight gradient: both operands token-major
-            if (sk) {
-                if (g16_km16(g16_tile, KM16_WGRAD_SK))
-                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, true, true, 3, 16>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
-                else
-                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, true, 1, true, true, 3, 32>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, dsk, g16_group_ring);
-            } else if (g16_km16(g16_tile, KM16_WGRAD_TILE))
-                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 2, true, true, 3, 16>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
-            else
-                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 2, true, true, 3, 32>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
-        } else {
-            if (d->a_layout || !d->b_layout) return DUPL_ERR_ARG;              // the data gradient: dy k-contiguous, W k-major
-            if (g16_km16(g16_tile, KM16_DGRAD_EPI)) {
-                const int f = epi_forms ? g16_epi_form_km(*d) : EPI_GENERIC;
-                if (f == EPI_D)
-                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 16, EPI_D>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
-                else if (f == EPI_A)
-                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 16, EPI_A>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
-                else
-                    DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 16>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
-            }
-            else
-                DUPL_LAUNCH((gemm_f16x3_km_kernel<2, 2, 4, 2, 2, false, 0, false, true, 3, 32>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
-        }
-        return dupl_launch_status();
-    }
-    if (d->fmt == 1) {
-        // format 1 operands: one accumulator set.  256 x 256 on 8 waves (wave tile 128 x 64, two LDS stages of 64 KB; tile 8) where
-        // the grid fills the chip, 256 x 128 (the ring kernel's tile with half the accumulators; 12) below.  One block per tile: the
-        // persistent form of 256 x 128 (14) measures the same or 1-3 % less, that of 256 x 256 spills (228 vs 353 TF/s-eq)
-        // (round 6, measured and dropped: the same 256 x 256 tile on FOUR waves of 128 x 128 -- one wave per SIMD in the 512-register
-        // file, 252 VGPRs + 256 accumulation registers, no spill, 16 instead of 24 fragment reads per 48 MFMAs -- is 8-20 % SLOWER on
-        // every forward shape, alone and next to a second stream (15 696 x 3 072 x 768 bias + GELU -> planes: 247 vs 300 TF/s-eq,
-        // 15 696 x 768 x 3 072 bias + residual: 295 vs 328; profiles/r06_tile16.txt): with one wave per SIMD nothing covers a wave's
-        // own waits, the result tile 7 gave in round 3)
-        const int nb21 = ((d->M + 255) / 256) * ((d->N + 127) / 128);
-        // (18 / 22: the same two tiles on the 16x16x32 MFMA, gemm_f16x3_ring16_kernel; the launcher's own choice, since the clock the
-        // chip holds under this loop is higher on that shape.  Both tiles switch together: they are bit-identical to each other)
-        int t = (g16_tile == 8 || g16_tile == 12 || g16_tile == 14 || g16_tile == 18 || g16_tile == 22) ? g16_tile : g16_tile16(*d);
-        if (d->K / TBK < 3 && t == 14) t = 12;
-        if (t == 18 || t == 22) {
-            static const g16_kernel_t big[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2>, gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_P>,
-                                                gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_G>, gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, 2, 3, EPI_R>};
-            static const g16_kernel_t small[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3>, gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_P>,
-                                                  gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_G>, gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, 3, 3, EPI_R>};
-            g16_launch16(*d, t, g16_tile == 0, g16_group_ring, s, big, small, epi_forms);
-        }
-        else if (t == 8) DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 4, 2, 2, true>), blocks(256, 256), dim3(512), 0, s, *d, g16_group_ring);
-        else if (t == 12) DUPL_LAUNCH((gemm_f16x3_ring_kernel<2, 2, 4, 2, 2, 3, true>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
-        else
-            DUPL_LAUNCH((gemm_f16x3_pring_kernel<2, 2, 4, 2, 2, false, true, 3>), persist_grid(nb21), dim3(512), 0, s, *d, g16_group_ring);
-        return dupl_launch_status();
-    }
-    if (tile == 10 && (accum || d->K / TBK < 3)) tile = 6;      // the persistent kernel has no split-K and a 3-stage prologue
-    if (tile == 11 && (!accum || d->deterministic || d->K / TBK < 8)) tile = accum ? 5 : 6;   // stream-K: atomics, pieces >= 3 k-steps
-    if (tile == 11) {
-        DUPL_LAUNCH((gemm_f16x3_pring_kernel<2, 2, 4, 2, 2, true>), dim3((unsigned)g16_persist_blocks), dim3(512), 0, s, *d,
-                           g16_group_ring);
-        return dupl_launch_status();
-    }
-    if (tile == 10) {
-        DUPL_LAUNCH((gemm_f16x3_pring_kernel<2, 2, 4, 2, 2>), persist_grid(((d->M + 255) / 256) * ((d->N + 127) / 128)), dim3(512), 0, s, *d,
-                    g16_group_ring);
-        return dupl_launch_status();
-    }
-    if (tile == 8 || tile == 12 || tile == 14 || tile == 18 || tile == 22) tile = 5;      // single-accumulator tiles: format 1 operands only (above)
-    if (tile == 6) DUPL_LAUNCH((gemm_f16x3_ring_kernel<2, 2, 4, 2, 2>), blocks(256, 128), dim3(512), 0, s, *d, g16_group_ring);
-    else if (tile == 7) DUPL_LAUNCH((gemm_f16x3_ring_kernel<4, 2, 2, 2, 1>), blocks(256, 128), dim3(256), 0, s, *d, g16_group_ring);
-    else if (tile == 3) DUPL_LAUNCH((gemm_f16x3_kernel<2, 1, 2, 2, 2>), blocks(128, 64), dim3(256), 0, s, *d, g16_group_m);
-    else DUPL_LAUNCH((gemm_f16x3_kernel<2, 1, 2, 4, 4>), blocks(128, 128), dim3(512), 0, s, *d, g16_group_m);
+    if (!g16_check(*d, single)) return DUPL_ERR_ARG;
+    g16_plan pl;
+    g16_choose(pl, *d, single);
+    for (int i = 0; i < pl.n; ++i) DUPL_LAUNCH(pl.l[i].kernel, pl.l[i].grid, pl.l[i].block, 0, (hipStream_t)stream, *pl.l[i].d, pl.l[i].group);
     return dupl_launch_status();
 }
 
-// products = 1: the single-product forward, gemm_f16x3_ring16_kernel<.., NP = 1> on the tiles and with the row split of the format 1
-// forward (g16_launch16).
-#ifndef G16H_STAGES
-#define G16H_STAGES 4   // ring depth of both tiles (4 x 32 KB / 4 x 24 KB)
-#endif
-static int g16_launch_hi(const dupl_gemm16_desc& d, const int tile, const int group, hipStream_t s) {
+static void g16_choose_hi(g16_plan& pl, const dupl_gemm16_desc& d, const g16_tile_t& t, const int group) {
     // (the generic epilogue only: NP = 1 has no forms)
     static const g16_kernel_t small[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<2, 2, 4, 2, 2, G16H_STAGES, 1>, nullptr, nullptr, nullptr};
     static const g16_kernel_t big[EPI_FWD_COUNT] = {gemm_f16x3_ring16_kernel<4, 2, 2, 4, 2, G16H_STAGES, 1>, nullptr, nullptr, nullptr};
-    g16_launch16(d, (tile == 18 || tile == 22) ? tile : g16_tile16(d), tile == 0, group, s, big, small, false);
-    return dupl_launch_status();
+    g16_choose16(pl, d, (t.family == 18 || t.family == 22) ? t.family : g16_tile16(d), t.family == 0, group, big, small, false);
 }
+

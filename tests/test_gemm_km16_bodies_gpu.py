@@ -173,6 +173,91 @@ def test_wgrad_grouped(dev, tokens, more_rows):
             assert torch.equal(t, b + a), tile
 
 
+# ------------------------------------------------------------------------------------------ a block walks more than one piece
+# 9 tiles of 256 x 128 (3 row tiles x 3 column tiles; group 2: the last row group is ragged) on a grid of 8 blocks: the block of XCD 0
+# walks two tiles (a next piece, then none), the others one.  Which block computes a tile does not enter its arithmetic.
+WALK = dict(persist_blocks=8, group=2)
+
+
+def _bits(t):
+    return t.view(torch.int32)
+
+
+@pytest.mark.parametrize("tile", BODIES)
+@pytest.mark.parametrize("dgelu", [False, True], ids=["linear", "dgelu"])
+def test_walk_dgrad_full_epilogue(dev, tile, dgelu):
+    """513 tokens x n_in 264 x n_out 96 on 8 blocks: bit-identical to the default grid, the amax word included."""
+    from dupl_amd import ops
+    o = _operands(513, 96, 264)
+    pre = o["pre"] if dgelu else None
+    got = {}
+    for name, extra in (("default", dict(group=2)), ("walk", WALK)):
+        dx, _ = ops.linear16(o["dy16"].rows_slice(0, 513), o["W16"], alpha=o["alpha"], dgelu_of=pre, b_kmajor=True, amax_for_next=True,
+                             tuning=_tn(tile, **extra))
+        ring = ops._scale_ring(dev)
+        assert dx._dupl_amax is ring[2]
+        word = ring[0][ring[1], 2].clone()
+        ops.split_prepare(dx, scaled=True, want_rm=True, want_T=False)      # (closes the reservation)
+        assert float(word) == float(dx.abs().max()) > 0
+        got[name] = (dx, word)
+    assert torch.equal(_bits(got["walk"][0]), _bits(got["default"][0]))
+    assert torch.equal(_bits(got["walk"][1]), _bits(got["default"][1]))
+
+
+@pytest.mark.parametrize("tile", BODIES)
+def test_walk_wgrad_one_owner(dev, tile):
+    """n_out 520 x n_in 264 over 97 tokens (Kp 128), the one-owner form (deterministic mode) on 8 blocks: bit-identical to the default grid."""
+    from dupl_amd import ops
+    o = _operands(97, 520, 264)
+    assert o["Kp"] == 128
+    base = _wgrad_single(o, ops.zeros((520, 264), dev), 1, tile, group=2)
+    walk = _wgrad_single(o, ops.zeros((520, 264), dev), 1, tile, **WALK)
+    assert float(base.abs().max()) > 0
+    assert torch.equal(_bits(walk), _bits(base))
+
+
+@pytest.mark.parametrize("sk", [0, -1], ids=["host-choice", "equal-runs"])
+def test_walk_stream_k_equal_runs(dev, sk):
+    """Contraction 288 = 9 k-steps, 9 tiles on 8 blocks: more tiles than blocks, so the host takes the equal-run cut (sk_slices 0) as it
+    does when asked for it (-1).  Runs of 81 / 8 k-steps span tiles, and cuts that land within 2 k-steps of a tile's edge are moved.
+    Data gradient into zeros and weight gradient, both bodies, the standing bar."""
+    from dupl_amd import ops
+    o = _operands(513, 288, 264)
+    want = o["dy_r"] @ o["W_r"]
+    e32 = _err(ops.linear_dgrad(o["dy32"], o["W32"]), want)
+    outs = {}
+    for tile in BODIES:
+        outs[tile] = ops.zeros((513, 264), dev)
+        ops.linear16(o["dy16"].rows_slice(0, 513), o["W16"], out=outs[tile], accumulate=True, alpha=o["alpha"], b_kmajor=True,
+                     tuning=_tn(tile, sk_slices=sk, **WALK))
+    _both(f"walk stream-K dgrad 513x264x288 sk_slices={sk}", outs, want, e32)
+    o = _operands(257, 520, 264)
+    assert o["Kp"] == 288
+    want = o["dy_r"].t() @ o["x_r"]
+    e32 = _err(_wgrad_f32(o, (520, 264), dev), want)
+    outs = {tile: _wgrad_single(o, ops.zeros((520, 264), dev), 0, tile, sk_slices=sk, **WALK) for tile in BODIES}
+    _both(f"walk stream-K wgrad 520x264x257 sk_slices={sk}", outs, want, e32)
+
+
+def test_walk_stream_k_aligned_slices(dev):
+    """sk_slices 2 with n_in 8: 3 tiles -> 6 (tile, slice) units on 8 blocks, two blocks return at once.  Slices of 5 and 4 k-steps."""
+    from dupl_amd import ops
+    o = _operands(513, 288, 8)
+    want = o["dy_r"] @ o["W_r"]
+    e32 = _err(ops.linear_dgrad(o["dy32"], o["W32"]), want)
+    outs = {}
+    for tile in BODIES:
+        outs[tile] = ops.zeros((513, 8), dev)
+        ops.linear16(o["dy16"].rows_slice(0, 513), o["W16"], out=outs[tile], accumulate=True, alpha=o["alpha"], b_kmajor=True,
+                     tuning=_tn(tile, sk_slices=2, **WALK))
+    _both("walk stream-K dgrad 513x8x288 sk_slices=2", outs, want, e32)
+    o = _operands(257, 520, 8)
+    want = o["dy_r"].t() @ o["x_r"]
+    e32 = _err(_wgrad_f32(o, (520, 8), dev), want)
+    outs = {tile: _wgrad_single(o, ops.zeros((520, 8), dev), 0, tile, sk_slices=2, **WALK) for tile in BODIES}
+    _both("walk stream-K wgrad 520x8x257 sk_slices=2", outs, want, e32)
+
+
 # ------------------------------------------------------------------------------------------ two streams
 @pytest.mark.parametrize("tile", BODIES)
 def test_bodies_are_deterministic_under_stream_concurrency(dev, tile):

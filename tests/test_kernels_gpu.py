@@ -1180,6 +1180,48 @@ def test_stream_k_weight_gradient(dev, M, N, K):
     assert e11 <= 2.0 * e5 + 1e-7
 
 
+# 9 tiles of 256 x 128 (513 x 264: 3 row tiles x 3 column tiles; group 2: the last row group is ragged) on a grid of 8 blocks: the block of
+# XCD 0 walks two pieces, the others one
+@pytest.mark.parametrize("tile,exp", [(10, 0), (14, 3)], ids=["format0-tile10", "format1-tile14"])
+def test_persistent_kernel_walks_two_tiles(dev, tile, exp):
+    """The persistent 256 x 128 kernels (tile 10: format 0, tile 14: format 1) at 513 x 264 x 96 on 8 blocks: bit-identical to the default
+    grid -- which block computes a tile does not enter its arithmetic."""
+    from dupl_amd import ops
+    g = torch.Generator().manual_seed(tile)
+    A = torch.randn(513, 96, generator=g).to(dev)
+    B = torch.randn(264, 96, generator=g).to(dev)
+    bias = torch.randn(264, generator=g).to(dev)
+    A16, B16 = ops.split16(A, exp=exp), ops.split16(B, exp=exp)
+    base, _ = ops.linear16(A16, B16, bias, tuning=dict(ops.GEMM16_TUNING, tile=tile, group=2))
+    walk, _ = ops.linear16(A16, B16, bias, tuning=dict(ops.GEMM16_TUNING, tile=tile, group=2, persist_blocks=8))
+    assert float(base.abs().max()) > 0
+    assert torch.equal(walk.view(torch.int32), base.view(torch.int32))
+
+
+@pytest.mark.parametrize("sk_slices", [0, 2])
+def test_stream_k_weight_gradient_walks_tiles(dev, sk_slices):
+    """Tile 11 at 513 x 264 x 288 (9 k-steps) on 8 blocks, onto existing content: runs of 81 / 8 k-steps span tiles, and cuts within 2
+    k-steps of a tile's edge are moved.  The bar of test_stream_k_weight_gradient.  sk_slices = 2 in the tuning is the same launch: the
+    format 0 kernel takes the equal-run cut whatever the tuning default says."""
+    from dupl_amd import ops
+    M, N, K = 513, 264, 288
+    g = torch.Generator().manual_seed(M * 7 + N * 3 + K)
+    A = torch.randn(M, K, generator=g).to(dev)
+    B = torch.randn(N, K, generator=g).to(dev)
+    A16, B16 = ops.split16(A), ops.split16(B)
+    c0 = torch.randn(M, N, generator=g).to(dev)
+    ref = c0.double() + A.double() @ B.double().t()
+    outs = {}
+    for tile in (5, 11):
+        c = c0.clone()
+        ops.linear16(A16, B16, out=c, accumulate=True, tuning=dict(ops.GEMM16_TUNING, tile=tile, group=2, persist_blocks=8, sk_slices=sk_slices))
+        outs[tile] = c
+    sc = float(ref.abs().max())
+    e5, e11 = (float((outs[t].double() - ref).abs().max()) / sc for t in (5, 11))
+    print(f"wgrad {M}x{N}x{K} on 8 blocks, sk_slices {sk_slices}: tile 5 {e5:.2e} stream-K {e11:.2e}")
+    assert e11 <= 2.0 * e5 + 1e-7
+
+
 def test_split_prepare_multi_equals_single_launches(dev):
     """dupl_split_prepare_multi: up to 16 unscaled matrices per launch (the x^T / W^T operands of one transformer block's
     backward) -- bit-identical planes to one dupl_split_prepare each; ragged shapes, row padding, > 16 items."""

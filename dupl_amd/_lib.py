@@ -229,6 +229,20 @@ class SegRegionsCleanDesc(ctypes.Structure):
         self.struct_size = ctypes.sizeof(SegRegionsCleanDesc)
 
 
+class SegBoundaryDesc(ctypes.Structure):
+    """Mirror of `dupl_seg_boundary_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("num_classes", ctypes.c_int32),
+        ("max_dist", ctypes.c_int32), ("biou_dist", ctypes.c_int32),
+        ("gt", ctypes.c_void_p), ("pred", ctypes.c_void_p), ("band_hist", ctypes.c_void_p), ("biou", ctypes.c_void_p),
+        ("dist_gt", ctypes.c_void_p), ("dist_pred", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(SegBoundaryDesc)
+
+
 GEMM_A_MCONTIG, GEMM_B_NCONTIG, GEMM_GELU, GEMM_ACCUM = 1, 2, 4, 8
 GEMM_MUL_DGELU, GEMM_RELU, GEMM_MUL_RELUMASK, GEMM_ABS, GEMM_STORE_PRE = 16, 32, 64, 128, 256
 GEMM_C_FRESH = 512            # DUPL_GEMM_C_FRESH (dupl_gemm_f16x3_group)
@@ -255,6 +269,7 @@ SEG_DECIDE_MAX_C = 255        # DUPL_SEG_DECIDE_MAX_C
 WINDOW_MAX = 256              # DUPL_WINDOW_MAX
 CRF_LATTICE_PIECE = 128       # DUPL_CRF_LATTICE_PIECE
 SEG_REGIONS_MAX_C, SEG_REGIONS_COLS = 256, 8  # DUPL_SEG_REGIONS_MAX_C, DUPL_SEG_REGIONS_COLS
+SEG_BOUNDARY_MAX_C, SEG_BOUNDARY_MAX_DIST = 255, 64   # DUPL_SEG_BOUNDARY_MAX_C, DUPL_SEG_BOUNDARY_MAX_DIST
 
 _PROTO = re.compile(r"^\s*int\s+(dupl_\w+)\s*\(([^;{]*)\)\s*;", re.M | re.S)
 
@@ -289,6 +304,8 @@ def _ctype(decl: str):
         return ctypes.POINTER(SegRegionsDesc)
     if "dupl_seg_regions_clean_desc" in d:
         return ctypes.POINTER(SegRegionsCleanDesc)
+    if "dupl_seg_boundary_desc" in d:
+        return ctypes.POINTER(SegBoundaryDesc)
     if "*" in d or d.startswith("dupl_stream_t"):
         return ctypes.c_void_p
     base = d.replace("const", "").split()
@@ -344,7 +361,8 @@ class _Lib:
         self.dupl_crf_lattice_workspace = self.cdll.dupl_crf_lattice_workspace
         self.dupl_crf_lattice_workspace.argtypes = [ctypes.POINTER(CrfLatticeDesc), ctypes.c_int32]
         self.dupl_crf_lattice_workspace.restype = ctypes.c_int64
-        for name, desc in (("dupl_seg_regions_workspace", SegRegionsDesc), ("dupl_seg_regions_clean_workspace", SegRegionsCleanDesc)):
+        for name, desc in (("dupl_seg_regions_workspace", SegRegionsDesc), ("dupl_seg_regions_clean_workspace", SegRegionsCleanDesc),
+                           ("dupl_seg_boundary_workspace", SegBoundaryDesc)):
             fn = getattr(self.cdll, name)
             fn.argtypes, fn.restype = [ctypes.POINTER(desc)], ctypes.c_int64
             setattr(self, name, fn)

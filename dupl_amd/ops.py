@@ -1462,3 +1462,52 @@ def seg_regions_clean(label: Tensor, *, min_area: int, connectivity: int = 8, ig
     region, n, table = seg_regions(out, conf, connectivity=connectivity, ignore_index=ignore_index, max_regions=max_regions,
                                    stats=stats, num_classes=C)
     return out, region, n, table, changed
+
+
+# ------------------------------------------------------------------------------------------ boundary scores (csrc/boundary.hip)
+def seg_boundary(gt: Tensor, pred: Tensor, *, num_classes: int, max_dist: int, biou_dist: int = 0, band_hist: Optional[Tensor] = None,
+                 biou: Optional[Tensor] = None, want_dist: bool = False):
+    """One image's boundary counters on the device (csrc/boundary.hip).  gt, pred (H,W) int64; a gt pixel is valid when
+    0 <= gt < num_classes, a pixel whose pred is outside that range is skipped.  dist(L)[p] = the Chebyshev distance from p to the nearest
+    pixel inside the image with another label (every value outside [0, num_classes) is one label); dist_b counts the image border too.
+      band_hist (R+1, nc, nc) int64 += 1 at [min(dist(gt), R+1) - 1, gt, pred] per valid pixel, R = max_dist (1 .. 64): summed over the
+        bins it is what confusion_accum adds, its first r bins are the confusion matrix of the trimap of width r;
+      biou (3, nc) int64 += the Boundary IoU counters I, G, P at distance biou_dist (1 .. 64; 0 = none, biou is left alone);
+      want_dist: also return dist(gt) and dist(pred) as (H,W) uint8 maps capped at R + 1.
+    band_hist / biou are allocated (zeroed) when not given.  Argument errors raise ValueError before anything is written.
+    Returns (band_hist, biou or None, dist_gt or None, dist_pred or None).  No synchronisation with the device."""
+    nc, R, d = int(num_classes), int(max_dist), int(biou_dist)
+    if not 1 <= nc <= _lib.SEG_BOUNDARY_MAX_C:
+        raise ValueError(f"seg_boundary takes 1 .. {_lib.SEG_BOUNDARY_MAX_C} classes, got {num_classes}")
+    if not 1 <= R <= _lib.SEG_BOUNDARY_MAX_DIST:
+        raise ValueError(f"max_dist must be 1 .. {_lib.SEG_BOUNDARY_MAX_DIST}, got {max_dist}")
+    if not 0 <= d <= _lib.SEG_BOUNDARY_MAX_DIST:
+        raise ValueError(f"biou_dist must be 0 .. {_lib.SEG_BOUNDARY_MAX_DIST}, got {biou_dist}")
+    for name, t in (("gt", gt), ("pred", pred)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.int64 and t.dim() == 2):
+            raise ValueError(f"{name} must be an (H,W) int64 device tensor, got "
+                             f"{(tuple(t.shape), t.dtype, t.device) if isinstance(t, torch.Tensor) else type(t)}")
+    if gt.shape != pred.shape or gt.device != pred.device:
+        raise ValueError(f"gt and pred must have one shape and device, got {tuple(gt.shape)} and {tuple(pred.shape)}")
+    H, W = gt.shape
+    if H < 1 or W < 1 or H * W > 0x7ffffff0:
+        raise ValueError(f"seg_boundary needs 1 .. 2^31 - 16 pixels, got {(H, W)}")
+    dev = gt.device
+    for name, t, shape in (("band_hist", band_hist, (R + 1, nc, nc)), ("biou", biou if d > 0 else None, (3, nc))):
+        if t is not None and not (t.is_cuda and t.device == dev and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == shape):
+            raise ValueError(f"{name} must be a contiguous {shape} int64 tensor on {dev}, got {tuple(t.shape)} {t.dtype} on {t.device}")
+    gt, pred = gt.contiguous(), pred.contiguous()
+    if band_hist is None:
+        band_hist = torch.zeros((R + 1, nc, nc), device=dev, dtype=torch.int64)
+    if d > 0 and biou is None:
+        biou = torch.zeros((3, nc), device=dev, dtype=torch.int64)
+    dg = torch.empty((H, W), device=dev, dtype=torch.uint8) if want_dist else None
+    dp = torch.empty((H, W), device=dev, dtype=torch.uint8) if want_dist else None
+    desc = _lib.SegBoundaryDesc(H=H, W=W, num_classes=nc, max_dist=R, biou_dist=d, gt=gt.data_ptr(), pred=pred.data_ptr(),
+                                band_hist=band_hist.data_ptr(), biou=_p(biou) if d > 0 else None, dist_gt=_p(dg), dist_pred=_p(dp))
+    nbytes = L().dupl_seg_boundary_workspace(ctypes.byref(desc))
+    assert nbytes > 0
+    ws = torch.empty((nbytes,), device=dev, dtype=torch.uint8)
+    desc.workspace, desc.workspace_bytes = ws.data_ptr(), nbytes
+    L().dupl_seg_boundary(ctypes.byref(desc), _stream())
+    return band_hist, (biou if d > 0 else None), dg, dp

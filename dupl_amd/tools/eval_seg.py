@@ -13,7 +13,12 @@ student's saved logits, `seg_crf` scores and the prediction PNGs.  It is the exa
 package, csrc/crf.hip), not pydensecrf's lattice approximation, and its scores have not been compared with pydensecrf's.
 Beyond the reference, `--ensemble 1` also scores the mean of the two students' class probabilities: per image one fused pass
 (ops.seg_ensemble, csrc/seg_ens.hip) up-samples both students' logits and fills the three confusion matrices and the students'
-agreement counters; `--crf_branch ens` runs the CRF stage on that mean.  Without these flags nothing changes."""
+agreement counters; `--crf_branch ens` runs the CRF stage on that mean.  `--boundary 1` also scores every column at the object
+boundaries: per image and column one fused pass (ops.seg_boundary, csrc/boundary.hip) splits the confusion matrix by the Chebyshev
+distance to the nearest ground-truth label change and fills the Boundary IoU counters (Cheng et al., CVPR 2021); the trimap mIoU of
+every `--trimap_widths` width (DeepLab's trimap score) and the Boundary IoU are printed under the table, returned under the key
+"boundary" of every score dict and, with `--crf 1`, reported for seg_crf too, so the CRF's effect at the boundary reads off one run.
+`--crf_method {exact,lattice}` chooses the CRF stage's inference (utils/dcrf.py).  Without these flags nothing changes."""
 from collections import OrderedDict
 
 import torch
@@ -87,6 +92,15 @@ def msc_seg_logits_coco(model, inputs, scales=(1.0, 1.25, 1.5), size=448):
     return accs[0], accs[1]
 
 
+def _ensemble_update(em, bms, seg, labels):
+    """One image into the EnsembleMatrix; with boundary matrices the same fused pass also hands back the ensemble's prediction for bms[2]."""
+    if not bms:
+        return em.update(seg[0], seg[1], labels)
+    gt = labels.reshape(labels.shape[-2:])
+    pred, _ = ops.seg_ensemble(seg[0], seg[1], gt.shape, gt=gt, hist=em.hist, counts=em.counts, want_pred=True)
+    bms[2].update(gt, pred)
+
+
 def _ensemble_scores(em):
     """[student 1, student 2, ensemble] of an EnsembleMatrix; the ensemble's dict also carries "agree", the share of the valid
     pixels on which the two students predict the same class."""
@@ -95,18 +109,52 @@ def _ensemble_scores(em):
     return sc
 
 
-def validate_coco(model, data_loader, args, num_classes=81, cat_list=None, process_group=None, keep_logits=None, ensemble=False):
+def parse_trimap_widths(text):
+    """--trimap_widths: "1,2,4" -> (1, 2, 4); positive integers, ascending, at most evaluate.BOUNDARY_MAX_DIST."""
+    import argparse
+    try:
+        widths = tuple(int(v) for v in str(text).strip("()[] ").split(","))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"trimap widths are integers separated by commas, got {text!r}")
+    if not widths or widths[0] < 1 or widths[-1] > evaluate.BOUNDARY_MAX_DIST or any(b <= a for a, b in zip(widths, widths[1:])):
+        raise argparse.ArgumentTypeError(f"trimap widths must be ascending integers in 1 .. {evaluate.BOUNDARY_MAX_DIST}, got {text!r}")
+    return widths
+
+
+def boundary_scores(bm, widths):
+    """The "boundary" entry of a score dict, from a filled evaluate.BoundaryMatrix: {"biou": mean Boundary IoU, "biou_iou": {class: value},
+    "trimap": {width: {"miou", "pAcc"} of the pixels at most `width` away from a ground-truth label change}}."""
+    b = bm.boundary_iou()
+    return {"biou": b["biou"], "biou_iou": b["iou"],
+            "trimap": {r: {"miou": s["miou"], "pAcc": s["pAcc"]} for r, s in bm.trimap_scores(widths).items()}}
+
+
+def format_boundary(scores, name_list):
+    """One line per column: the Boundary IoU and the trimap mIoU per width (x 100, as the table above it)."""
+    return "\n".join(f"boundary {n}: BIoU {100 * s['boundary']['biou']:.3f} | trimap mIoU " +
+                     " ".join(f"@{r} {100 * t['miou']:.3f}" for r, t in s["boundary"]["trimap"].items())
+                     for s, n in zip(scores, name_list))
+
+
+def _boundary_matrices(boundary, n, num_classes, dev):
+    return [evaluate.BoundaryMatrix(num_classes, dev, max_dist=max(boundary)) for _ in range(n)] if boundary else None
+
+
+def validate_coco(model, data_loader, args, num_classes=81, cat_list=None, process_group=None, keep_logits=None, ensemble=False,
+                  boundary=None):
     """eval_seg_coco_ddp._validate on this rank's shard of the loader (the reference splits the val set round-robin over
     the ranks, tools/eval_seg_coco_ddp.py:239-245, and every rank scores its own shard).  With `process_group` (or an
     initialised default group) the per-rank confusion matrices are additionally summed over the ranks -- nc^2 int64
     counters, the only exchange of the evaluation path -- so that every rank returns the scores of the WHOLE set.
     ensemble=True: one fused pass per image (ops.seg_ensemble) up-samples both students' logits, scores each student and the mean
-    of their class probabilities -> (seg_score_1, seg_score_2, seg_score_ens); the students' scores are the same counts."""
+    of their class probabilities -> (seg_score_1, seg_score_2, seg_score_ens); the students' scores are the same counts.
+    boundary=widths: every column also feeds an evaluate.BoundaryMatrix and its score dict gains "boundary" (boundary_scores)."""
     import torch.distributed as dist
     from ..utils.train_helper import _device_of, _fetch
     dev = _device_of(model)
     cms = [evaluate.ConfusionMatrix(num_classes, dev) for _ in range(2)]
     em = evaluate.EnsembleMatrix(num_classes, dev) if ensemble else None
+    bms = _boundary_matrices(boundary, 3 if ensemble else 2, num_classes, dev)
     model.eval()
     scales = getattr(args, "scales", (1.0, 1.25, 1.5))
     for data in data_loader:
@@ -114,59 +162,80 @@ def validate_coco(model, data_loader, args, num_classes=81, cat_list=None, proce
         seg = msc_seg_logits_coco(model, inputs, scales, getattr(args, "crop_size", 448))
         H, W = labels.shape[1:]
         if ensemble:
-            em.update(seg[0], seg[1], labels)
+            _ensemble_update(em, bms, seg, labels)
         for k in range(2):
+            if not ensemble or bms:
+                pred = ops.upsample_argmax(seg[k], H, W)
             if not ensemble:
-                cms[k].update(labels, ops.upsample_argmax(seg[k], H, W))
+                cms[k].update(labels, pred)
+            if bms:
+                bms[k].update(labels, pred)
             if keep_logits is not None:          # eval_seg_coco_ddp.py:127-128 saves the summed low-resolution logits
                 keep_logits(data[0], k + 1, seg[k])
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
-        for t in ([em.hist, em.counts] if ensemble else [c.hist for c in cms]):
+        for t in ([em.hist, em.counts] if ensemble else [c.hist for c in cms]) + [t for b in bms or [] for t in (b.hist, b.biou)]:
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
     sc = _ensemble_scores(em) if ensemble else [c.scores() for c in cms]
+    for s, b in zip(sc, bms or []):
+        s["boundary"] = boundary_scores(b, boundary)
     if cat_list is not None:
         print(format_tabs(sc, ["Seg_1", "Seg_2", "Seg_ens"][:len(sc)], cat_list=cat_list))
+        if bms:
+            print(format_boundary(sc, ["Seg_1", "Seg_2", "Seg_ens"]))
     return tuple(sc)
 
 
-def validate(model, data_loader, args, num_classes=21, cat_list=None, keep_logits=None, ensemble=False):
+def validate(model, data_loader, args, num_classes=21, cat_list=None, keep_logits=None, ensemble=False, boundary=None):
     """eval_seg_voc._validate: multi-scale seg predictions of both students over a loader of
     (name, inputs (1,3,h,w), labels (1,H,W), cls_label) -> (seg_score_1, seg_score_2).
     keep_logits(name, branch, logits) is called with the (1,C1,H,W) device logits (the reference np.save()s them for the
     CRF stage).  ensemble=True: one fused pass per image (ops.seg_ensemble) scores each student and the mean of their class
-    probabilities -> (seg_score_1, seg_score_2, seg_score_ens); the students' scores are the same counts."""
+    probabilities -> (seg_score_1, seg_score_2, seg_score_ens); the students' scores are the same counts.
+    boundary=widths: every column also feeds an evaluate.BoundaryMatrix and its score dict gains "boundary" (boundary_scores)."""
     from ..utils.train_helper import _device_of, _fetch
     dev = _device_of(model)
     cms = [evaluate.ConfusionMatrix(num_classes, dev) for _ in range(2)]
     em = evaluate.EnsembleMatrix(num_classes, dev) if ensemble else None
+    bms = _boundary_matrices(boundary, 3 if ensemble else 2, num_classes, dev)
     model.eval()
     for data in data_loader:
         inputs, labels, _ = _fetch(data, dev)
         seg = msc_seg_logits(model, inputs, labels.shape[1:], getattr(args, "scales", (1.0, 1.5, 1.25)))
         if ensemble:
-            em.update(seg[0], seg[1], labels)
+            _ensemble_update(em, bms, seg, labels)
         for k in range(2):
+            if not ensemble or bms:
+                pred = ops.argmax_channels(seg[k])
             if not ensemble:
-                cms[k].update(labels, ops.argmax_channels(seg[k]))
+                cms[k].update(labels, pred)
+            if bms:
+                bms[k].update(labels, pred)
             if keep_logits is not None:
                 keep_logits(data[0], k + 1, seg[k])
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         # main() shards the split over the ranks for both datasets: the score is of the summed confusion matrices
-        for t in ([em.hist, em.counts] if ensemble else [c.hist for c in cms]):
+        for t in ([em.hist, em.counts] if ensemble else [c.hist for c in cms]) + [t for b in bms or [] for t in (b.hist, b.biou)]:
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
     sc = _ensemble_scores(em) if ensemble else [c.scores() for c in cms]
+    for s, b in zip(sc, bms or []):
+        s["boundary"] = boundary_scores(b, boundary)
     if cat_list is not None and (not dist.is_initialized() or dist.get_rank() == 0):
         print(format_tabs(sc, ["Seg_1", "Seg_2", "Seg_ens"][:len(sc)], cat_list=cat_list))
+        if bms:
+            print(format_boundary(sc, ["Seg_1", "Seg_2", "Seg_ens"]))
     return tuple(sc)
 
 
-def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb_dir, num_classes, dev, process_group=None):
+def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb_dir, num_classes, dev, process_group=None,
+             boundary=None, method=None):
     """tools/eval_seg_voc.py:94-153 / tools/eval_seg_coco_ddp.py:142-202 on the device, over this rank's `names`: per image the
     saved logits of `branch` are resized to the JPEG's size, softmax + DenseCRF(10, 1, 1, 4, 121, 5) + argmax run on the device,
     the label PNG (and the palette PNG) are written and a device ConfusionMatrix is accumulated; with several ranks the
     matrices are summed.  image_path(name) -> JPEG path; label_of(name, image) -> (H,W) ground truth.  Returns the scores.
-    branch "ens": both students' saved logits go through ops.seg_ensemble and the CRF runs on the mean of their probabilities."""
+    branch "ens": both students' saved logits go through ops.seg_ensemble and the CRF runs on the mean of their probabilities.
+    method "exact" / "lattice": the CRF's inference (None = utils.dcrf.METHOD).  boundary=widths: the predictions also feed an
+    evaluate.BoundaryMatrix and the returned dict gains "boundary" (boundary_scores)."""
     import os
     import numpy as np
     import torch.distributed as dist
@@ -174,7 +243,10 @@ def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb
     from ..utils import imutils
     from ..utils.dcrf import DenseCRF
     post = DenseCRF(iter_max=10, pos_xy_std=1, pos_w=1, bi_xy_std=121, bi_rgb_std=5, bi_w=4)
+    if method is not None:
+        post.method = method
     cm = evaluate.ConfusionMatrix(num_classes, dev)
+    bm = evaluate.BoundaryMatrix(num_classes, dev, max_dist=max(boundary)) if boundary else None
     for d in (segs_dir, segs_rgb_dir):
         if d:
             os.makedirs(d, exist_ok=True)
@@ -195,13 +267,19 @@ def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb
         pred = ops.argmax_channels(Q[None])[0]
         label = torch.from_numpy(np.ascontiguousarray(label_of(name, image)).astype(np.int64)).to(dev)
         cm.update(label, pred)
+        if bm is not None:
+            bm.update(label, pred)
         pred = pred.cpu().numpy().astype(np.uint8)
         Image.fromarray(pred).save(os.path.join(segs_dir, name + ".png"))
         if segs_rgb_dir:
             Image.fromarray(imutils.encode_cmap(pred).astype(np.uint8)).save(os.path.join(segs_rgb_dir, name + ".png"))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
-        dist.all_reduce(cm.hist, op=dist.ReduceOp.SUM, group=process_group)
-    return cm.scores()
+        for t in [cm.hist] + ([bm.hist, bm.biou] if bm is not None else []):
+            dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
+    sc = cm.scores()
+    if bm is not None:
+        sc["boundary"] = boundary_scores(bm, boundary)
+    return sc
 
 
 def build_parser(dataset: str = "voc"):
@@ -242,6 +320,15 @@ def build_parser(dataset: str = "voc"):
                    help="what --crf 1 post-processes: auto = the highest mIoU (of the two students, or with --ensemble 1 of the "
                         "students and the ensemble; on equal mIoU the students' rule, then the ensemble last), 1 / 2 = that "
                         "student, ens = the ensemble (needs --ensemble 1)")
+    p.add_argument("--crf_method", default=None, choices=("exact", "lattice"),
+                   help="the inference of the --crf 1 stage, for every --crf_branch: exact = the exact mean-field update, lattice = the "
+                        "permutohedral-lattice approximation (utils/dcrf.py); default: utils.dcrf.METHOD")
+    p.add_argument("--boundary", default=0, type=int, choices=(0, 1),
+                   help="1: also score every column at the object boundaries (one fused pass per image and column, ops.seg_boundary): "
+                        "a line per column with the Boundary IoU and the trimap mIoU per --trimap_widths width, '<column> BIoU' in the "
+                        "last line, a 'boundary' entry in every returned score dict; with --crf 1 for seg_crf too")
+    p.add_argument("--trimap_widths", default="1,2,4,8,16,32", type=parse_trimap_widths,
+                   help="the trimap widths --boundary 1 reports: positive integers, ascending, at most 64")
     p.add_argument("--nograd_gemm", default=os.environ.get("DUPL_NOGRAD_GEMM", "f16x3"), choices=("f16x3", "f16"),
                    help="GEMMs and attention of the no-grad encoder passes (multi-scale CAM, validation, inference): f16x3 = three f16 products, "
                         "fp32-equivalent (default); f16 = one product on the hi planes, fp32 accumulation (engine.set_nograd_gemm_mode; "
@@ -333,16 +420,21 @@ def main(argv=None):
             nm = name[0] if isinstance(name, (tuple, list)) else name
             np.save(os.path.join(logits_dir, f"branch{branch}", str(nm) + ".npy"), {"msc_seg": logits.cpu().numpy()})
 
+    boundary = args.trimap_widths if args.boundary else None
     with torch.no_grad():
         if is_voc:
-            sc = validate(model, loader, args, args.num_classes, voc.class_list, keep_logits=keep, ensemble=bool(args.ensemble))
+            sc = validate(model, loader, args, args.num_classes, voc.class_list, keep_logits=keep, ensemble=bool(args.ensemble),
+                          boundary=boundary)
         else:
-            sc = validate_coco(model, loader, args, args.num_classes, coco.class_list, keep_logits=keep, ensemble=bool(args.ensemble))
+            sc = validate_coco(model, loader, args, args.num_classes, coco.class_list, keep_logits=keep, ensemble=bool(args.ensemble),
+                               boundary=boundary)
     s1, s2 = sc[0], sc[1]
     ens = sc[2] if args.ensemble else None
     last = {"Seg_1 mIoU": s1["miou"], "Seg_2 mIoU": s2["miou"]}
     if ens is not None:
         last.update({"Seg_ens mIoU": ens["miou"], "agree": ens["agree"]})
+    if boundary:
+        last.update({f"{n} BIoU": s["boundary"]["biou"] for n, s in zip(("Seg_1", "Seg_2", "Seg_ens"), sc)})
     # crf_proc (eval_seg_voc.py:185-188): the student with the higher mIoU unless --crf_branch / --ensemble say otherwise
     branch = pick_crf_branch(args.crf_branch, s1, s2, ens)
     rank0 = int(os.environ.get("RANK", "0")) == 0
@@ -373,9 +465,12 @@ def main(argv=None):
         print("crf post-processing...")
     with torch.no_grad():
         crf = crf_proc(branch, names, image_path, label_of, logits_dir, os.path.join(base_dir, "segs/seg_preds", args.infer_set),
-                       rgb_dir, args.num_classes, dev)
+                       rgb_dir, args.num_classes, dev, boundary=boundary, method=args.crf_method)
     if rank0:
         print(format_tabs([crf], ["seg_crf"], cat_list=voc.class_list if is_voc else coco.class_list))
+        if boundary:
+            print(format_boundary([crf], ["seg_crf"]))
+            last["seg_crf BIoU"] = crf["boundary"]["biou"]
         print({**last, "seg_crf mIoU": crf["miou"]})
     return tuple(sc) + (crf,)
 

@@ -3,7 +3,8 @@
 Same functions and return values as the reference (`multilabel_score`, `_fast_hist`, `scores`, `pseudo_scores`) for
 host arrays, plus `ConfusionMatrix`: the histogram the reference rebuilds on the host from lists of per-image numpy maps
 (`scores(gts, preds)` at the end of validation) is accumulated on the device instead, image by image
-(csrc/eval.hip::confusion_kernel); only nc*nc counters are copied back."""
+(csrc/eval.hip::confusion_kernel); only nc*nc counters are copied back.  `BoundaryMatrix` (beyond the reference) does the same
+for the scores at the object boundaries: the trimap confusion matrices and the Boundary IoU counters (csrc/boundary.hip)."""
 import numpy as np
 import torch
 
@@ -117,3 +118,57 @@ class ThresholdSweep:
         sc = self.scores()
         i = max(range(len(sc)), key=lambda k: (sc[k]["miou"], -k))
         return self.thresholds[i], sc[i]
+
+
+BOUNDARY_MAX_DIST = 64      # DUPL_SEG_BOUNDARY_MAX_DIST: the farthest distance the boundary kernel searches
+
+
+def biou_dist(H, W):
+    """The Boundary IoU band width of an (H,W) image: the published code's dilation_ratio = 0.02 of the image diagonal, rounded to
+    the nearest integer with halves rounded up (375 x 500: 12.5 -> 13), at least 1, clipped to the kernel's maximum distance
+    BOUNDARY_MAX_DIST = 64 (reached by images with a diagonal of 3175 pixels and more)."""
+    d = int(np.floor(0.02 * np.sqrt(float(H) * float(H) + float(W) * float(W)) + 0.5))
+    return max(1, min(BOUNDARY_MAX_DIST, d))
+
+
+class BoundaryMatrix:
+    """Device-resident boundary counters, filled image by image by the fused pass ops.seg_boundary (csrc/boundary.hip):
+    hist (max_dist + 1, nc, nc) int64 -- the confusion matrix split by the distance of the pixel to the nearest ground-truth label
+    change (bin r - 1 = distance r, the last bin everything farther than max_dist) -- and biou (3, nc) int64, the Boundary IoU
+    counters I, G, P (Cheng et al., CVPR 2021) at the per-image distance biou_dist(H, W).  Both are plain sums: all-reduce them."""
+
+    def __init__(self, num_classes, device, max_dist=32):
+        self.num_classes, self.max_dist = int(num_classes), int(max_dist)
+        if not 1 <= self.max_dist <= BOUNDARY_MAX_DIST:
+            raise ValueError(f"max_dist must be 1 .. {BOUNDARY_MAX_DIST}, got {max_dist}")
+        self.hist = torch.zeros((self.max_dist + 1, self.num_classes, self.num_classes), device=device, dtype=torch.int64)
+        self.biou = torch.zeros((3, self.num_classes), device=device, dtype=torch.int64)
+
+    def update(self, gt, pred):
+        """gt, pred: (H,W) or (1,H,W) int64 device tensors of one image."""
+        H, W = gt.shape[-2:]
+        ops.seg_boundary(gt.reshape(H, W), pred.reshape(H, W), num_classes=self.num_classes, max_dist=self.max_dist,
+                         biou_dist=biou_dist(H, W), band_hist=self.hist, biou=self.biou)
+
+    def scores(self):
+        """The plain scores: the bins summed are the confusion matrix."""
+        return scores_from_hist(self.hist.sum(0).cpu().numpy())
+
+    def trimap_scores(self, widths):
+        """{r: score dict of the pixels at most r away from a ground-truth label change} for every r of widths (1 .. max_dist)."""
+        h = self.hist.cpu().numpy()
+        out = {}
+        for r in widths:
+            if not 1 <= int(r) <= self.max_dist:
+                raise ValueError(f"trimap width must be 1 .. {self.max_dist}, got {r}")
+            out[int(r)] = scores_from_hist(h[:int(r)].sum(0))
+        return out
+
+    def boundary_iou(self):
+        """{"biou": the nan-mean over the classes with ground-truth boundary pixels (G > 0), as miou uses only classes present in the
+        ground truth; nan when there is none, "iou": {class: I / (G + P - I)}}."""
+        I, G, P = (v.astype(np.float64) for v in self.biou.cpu().numpy())
+        with np.errstate(divide="ignore", invalid="ignore"):
+            iu = I / (G + P - I)
+        present = G > 0
+        return {"biou": float(np.nanmean(iu[present])) if present.any() else float("nan"), "iou": dict(zip(range(len(iu)), iu))}

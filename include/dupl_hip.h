@@ -918,6 +918,44 @@ typedef struct dupl_seg_regions_clean_desc {
 int64_t dupl_seg_regions_clean_workspace(const dupl_seg_regions_clean_desc* d);
 int dupl_seg_regions_clean(const dupl_seg_regions_clean_desc* d, dupl_stream_t stream);
 
+/* ------------------------------------------------------------------ boundary scores of one image (csrc/boundary.hip)
+ * Beyond the reference, whose evaluate.py scores the confusion matrix only.  A gt pixel is valid when 0 <= gt < num_classes; a pixel
+ * whose pred is outside that range is skipped in every counter.  dist(L)[p] = the smallest Chebyshev distance max(|dx|,|dy|) from p to a
+ * pixel q INSIDE the image with L[q] != L[p] (the image border does not count);  dist_b(L)[p] = min(dist(L)[p],
+ * min(x, y, W-1-x, H-1-y) + 1), the same with the border counted.  Every value outside [0, num_classes) is ONE label to its
+ * neighbours (VOC's 255 contour is simply a different label).
+ *   band_hist (R+1, nc, nc) int64, ADDED to: a valid pixel adds 1 to band_hist[min(dist(gt)[p], R+1) - 1][gt[p]][pred[p]]; bin R holds
+ *             everything farther than R = max_dist.  band_hist summed over the bins is what dupl_confusion_accum adds, and the first
+ *             r bins are the confusion matrix of the trimap of width r, for every r <= R from the one pass;
+ *   biou (3, nc) int64, ADDED to when biou_dist = d > 0, over valid pixels: row 0 I[c] where gt = pred = c, dist_b(gt) <= d and
+ *             dist_b(pred) <= d; row 1 G[c] where gt = c and dist_b(gt) <= d; row 2 P[c] where pred = c and dist_b(pred) <= d.
+ *             Boundary IoU (Cheng et al., CVPR 2021) of class c = I / (G + P - I); the bands are mask & ~erode(mask, 3x3, d times) of
+ *             the paper's mask_to_boundary;
+ *   dist_gt, dist_pred (H,W) uint8, WRITTEN when given: dist capped at R + 1.
+ * Three launches, no host synchronisation; the int64 maps are read once.  Integer atomics only, combined per workgroup first:
+ * bit-reproducible.  Scratch: `workspace` of at least dupl_seg_boundary_workspace(d) bytes, 4-byte aligned; its contents before and
+ * after the call mean nothing. */
+#define DUPL_SEG_BOUNDARY_MAX_C 255
+#define DUPL_SEG_BOUNDARY_MAX_DIST 64
+typedef struct dupl_seg_boundary_desc {
+    uint32_t struct_size;        /* sizeof(dupl_seg_boundary_desc), checked */
+    int32_t H, W;                /* >= 1 each, H W < 2^31 - 16 */
+    int32_t num_classes;         /* 1 .. DUPL_SEG_BOUNDARY_MAX_C */
+    int32_t max_dist;            /* R: 1 .. DUPL_SEG_BOUNDARY_MAX_DIST */
+    int32_t biou_dist;           /* d: 0 = no Boundary IoU counters, else 1 .. DUPL_SEG_BOUNDARY_MAX_DIST */
+    const int64_t* gt;           /* (H,W) */
+    const int64_t* pred;         /* (H,W) */
+    int64_t* band_hist;          /* (R+1, nc, nc) */
+    int64_t* biou;               /* (3, nc); required when biou_dist > 0 */
+    uint8_t* dist_gt;            /* (H,W); or NULL */
+    uint8_t* dist_pred;          /* (H,W); or NULL */
+    void* workspace;
+    int64_t workspace_bytes;
+} dupl_seg_boundary_desc;
+/* 6 x (H W rounded up to 256) bytes: two byte maps and two 16-bit maps of label | row distance << 8; <= 0 on a bad descriptor */
+int64_t dupl_seg_boundary_workspace(const dupl_seg_boundary_desc* d);
+int dupl_seg_boundary(const dupl_seg_boundary_desc* d, dupl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

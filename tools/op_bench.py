@@ -1,5 +1,5 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd | seg_render | predict | crf_lattice | regions
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd | seg_render | predict | crf_lattice | regions | boundary
 `crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81.
 `cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces.
 `seg_ensemble` (only when named) times the fused ensemble tail of tools/eval_seg --ensemble 1 (ops.seg_ensemble) against the composition
@@ -11,6 +11,10 @@ same label and confidence (VOC and COCO form, one and two students) and ops.seg_
 `regions` (only when named; then nothing else runs) times ops.seg_regions and ops.seg_regions_clean (min_area 64) against the host path
 (label.cpu() -> scipy.ndimage.label per class -> find_objects -> bincount) on a VOC-sized and a 1024 x 2048 prediction-like map and on
 a 1024 x 2048 single-label map, after asserting that ids, areas and boxes agree.
+`boundary` (only when named; then nothing else runs) times ops.seg_boundary (band histogram + Boundary IoU counters, R = 32) at 375x500x21
+and 480x640x81 against ops.confusion_accum on the same maps (what eval_seg --boundary 1 adds per image and column), against the host
+path (.cpu() -> the scipy filters and erosions of tests/boundary_ref.py, equality asserted first) and against the 16 B/px of reading the
+two int64 maps once; its three kernels are timed apart through a second call that stops after each of them.
 `predict` (only when named; then nothing else runs) times tools/predict on one synthetic 1024 x 2048 image, ViT-B, whole image against
 sliding windows, with the peak device memory of each.
 `backbone` (only when named; then nothing else runs) times one phase-B training step at VOC 448^2, 4 images, two student streams
@@ -344,6 +348,57 @@ def regions_bench(dev, g):
               f"{t_n:.1f} us; number + stats {t_all - t_n:.1f} us")
 
 
+def boundary_bench(dev, g):
+    """ops.seg_boundary into resident counters (what evaluate.BoundaryMatrix.update enqueues) on prediction-like maps: gt = the argmax
+    of a smooth seeded field with a 255 contour, pred = the argmax of the same field plus noise (it agrees inside the objects and
+    strays at their edges).  Floor: 16 B/px, the two int64 maps read once.  The kernels apart: rocprofv3 --kernel-trace --stats on
+    this mode (bd_pack_kernel, bd_row_kernel, bd_col_kernel)."""
+    import os
+    import time
+    import numpy as np
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import boundary_ref as BR
+    from dupl_amd.utils import evaluate
+
+    def maps(H, W, nc):
+        f = torch.randn((1, nc, H // 24 + 2, W // 24 + 2), generator=g)
+        up = lambda t: torch.nn.functional.interpolate(t, size=(H, W), mode="bilinear", align_corners=False)[0]
+        gt = up(f).argmax(0)
+        pred = up(f + 0.3 * torch.randn(f.shape, generator=g)).argmax(0)
+        edge = torch.zeros((H, W), dtype=torch.bool)
+        edge[:, 1:] |= gt[:, 1:] != gt[:, :-1]
+        edge[1:, :] |= gt[1:, :] != gt[:-1, :]
+        return torch.where(edge, torch.full_like(gt, 255), gt), pred
+
+    R = 32
+    for H, W, nc in ((375, 500, 21), (480, 640, 81)):
+        d = evaluate.biou_dist(H, W)
+        gt_h, pred_h = maps(H, W, nc)
+        gt, pred = gt_h.to(dev), pred_h.to(dev)
+        hist = torch.zeros((R + 1, nc, nc), device=dev, dtype=torch.int64)
+        biou = torch.zeros((3, nc), device=dev, dtype=torch.int64)
+        conf = torch.zeros((nc, nc), device=dev, dtype=torch.int64)
+        ops.seg_boundary(gt, pred, num_classes=nc, max_dist=R, biou_dist=d, band_hist=hist, biou=biou)
+
+        def host():
+            a, b = gt.cpu().numpy(), pred.cpu().numpy()
+            return BR.band_hist(a, b, nc, R), BR.biou_counts(a, b, nc, d)
+        t0 = time.perf_counter()
+        want = host()
+        t_h = (time.perf_counter() - t0) * 1e6
+        assert np.array_equal(hist.cpu().numpy(), want[0]) and np.array_equal(biou.cpu().numpy(), want[1])
+        near = int(want[0][:R].sum()) / max(int(want[0].sum()), 1)
+        floor = 16 * H * W
+        for i in range(3):
+            t_b = timeit(lambda: ops.seg_boundary(gt, pred, num_classes=nc, max_dist=R, biou_dist=d, band_hist=hist, biou=biou), n=300, warm=30)
+            t_t = timeit(lambda: ops.seg_boundary(gt, pred, num_classes=nc, max_dist=R, band_hist=hist), n=300, warm=30)
+            t_c = timeit(lambda: ops.confusion_accum(gt, pred, conf), n=300, warm=30)
+            print(f"boundary {H}x{W}x{nc} R={R} d={d} ({100 * near:.0f} % of the valid pixels within R), round {i}: seg_boundary {t_b:.1f} us "
+                  f"({t_b * 1e3 / (H * W):.3f} ns/px; floor {floor / 1e6:.2f} MB = {floor / 6.3e6:.1f} us at 6.3 TB/s, {floor / t_b / 1e6:.3f} TB/s "
+                  f"of it), without the Boundary IoU counters {t_t:.1f} us; confusion_accum alone {t_c:.1f} us (+{t_b - t_c:.1f} us per image and "
+                  f"column); host scipy path {t_h:.0f} us ({t_h / t_b:.0f}x)")
+
+
 def _count_only(label):
     """dupl_seg_regions asked for n_regions alone: the labelling launches without number and stats"""
     import ctypes
@@ -473,6 +528,8 @@ def main():
         return seg_render_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     if "regions" in sys.argv[1:]:
         return regions_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
+    if "boundary" in sys.argv[1:]:
+        return boundary_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     if "crf_lattice" in sys.argv[1:]:
         return crf_lattice_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}

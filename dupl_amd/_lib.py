@@ -243,6 +243,21 @@ class SegBoundaryDesc(ctypes.Structure):
         self.struct_size = ctypes.sizeof(SegBoundaryDesc)
 
 
+class SegCalibDesc(ctypes.Structure):
+    """Mirror of `dupl_seg_calib_desc` (include/dupl_hip.h)."""
+    _fields_ = [
+        ("struct_size", ctypes.c_uint32), ("C", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+        ("H", ctypes.c_int32), ("W", ctypes.c_int32), ("is_prob", ctypes.c_int32), ("T", ctypes.c_int32),
+        ("nbins", ctypes.c_int32), ("reserved0", ctypes.c_int32),
+        ("a", ctypes.c_void_p), ("b", ctypes.c_void_p), ("gt", ctypes.c_void_p), ("inv_temp", ctypes.c_void_p),
+        ("bins", ctypes.c_void_p), ("cls", ctypes.c_void_p), ("sums", ctypes.c_void_p),
+    ]
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        self.struct_size = ctypes.sizeof(SegCalibDesc)
+
+
 GEMM_A_MCONTIG, GEMM_B_NCONTIG, GEMM_GELU, GEMM_ACCUM = 1, 2, 4, 8
 GEMM_MUL_DGELU, GEMM_RELU, GEMM_MUL_RELUMASK, GEMM_ABS, GEMM_STORE_PRE = 16, 32, 64, 128, 256
 GEMM_C_FRESH = 512            # DUPL_GEMM_C_FRESH (dupl_gemm_f16x3_group)
@@ -270,6 +285,7 @@ WINDOW_MAX = 256              # DUPL_WINDOW_MAX
 CRF_LATTICE_PIECE = 128       # DUPL_CRF_LATTICE_PIECE
 SEG_REGIONS_MAX_C, SEG_REGIONS_COLS = 256, 8  # DUPL_SEG_REGIONS_MAX_C, DUPL_SEG_REGIONS_COLS
 SEG_BOUNDARY_MAX_C, SEG_BOUNDARY_MAX_DIST = 255, 64   # DUPL_SEG_BOUNDARY_MAX_C, DUPL_SEG_BOUNDARY_MAX_DIST
+SEG_CALIB_MAX_C, SEG_CALIB_MAX_T, SEG_CALIB_MAX_BINS = 255, 16, 64    # DUPL_SEG_CALIB_MAX_C, DUPL_SEG_CALIB_MAX_T, DUPL_SEG_CALIB_MAX_BINS
 
 _PROTO = re.compile(r"^\s*int\s+(dupl_\w+)\s*\(([^;{]*)\)\s*;", re.M | re.S)
 
@@ -306,6 +322,8 @@ def _ctype(decl: str):
         return ctypes.POINTER(SegRegionsCleanDesc)
     if "dupl_seg_boundary_desc" in d:
         return ctypes.POINTER(SegBoundaryDesc)
+    if "dupl_seg_calib_desc" in d:
+        return ctypes.POINTER(SegCalibDesc)
     if "*" in d or d.startswith("dupl_stream_t"):
         return ctypes.c_void_p
     base = d.replace("const", "").split()

@@ -14,36 +14,13 @@
 // otherwise 64-bit atomics straight to hist.  Integer atomics only: the result is bit-reproducible in either mode.
 // seg_decide_kernel (below) is the same pass without a ground truth, for tools/predict: winner, confidence, rejection, label bytes and
 // per-label statistics on the same tiles, for one student, two, or probabilities (DenseCRF's marginals).
-#include "common.h"
+#include "seg_pixel.h"                   // the tile, the tap, the exp and the staging: shared with seg_calib.hip
 #include "../../include/dupl_hip.h"
 
 namespace {
 
-constexpr int SE_THREADS = 256;
-constexpr int SE_TW = 64, SE_TH = 4;     // output tile: a wave per row segment, 256 contiguous bytes per channel of prob
 constexpr int SE_BINS = 20480;           // 16-bit counters, two to a word (40 KB): 3 * 82^2 = 20172
-constexpr int SE_STAGE = 6144;           // floats of staged source pixels (24 KB): COCO 84 x 2 x (3 x 5) = 2520
 constexpr int SE_BLOCK_TILES = 255;      // tiles per workgroup at most: 255 * 256 pixels cannot overflow a 16-bit counter
-
-// The students' predictions must be the bits of upsample_argmax_kernel (eval.hip), so the source index and the tap are that kernel's
-// arithmetic with every rounding pinned to what hipcc makes of it there: r = fma(scale, o + 0.5, -0.5);
-// v = hy * (hx a + lx b) + ly * (hx c + lx d) with top = fma(hx, a, lx b), bot = fma(hx, c, lx d) and a plain hy top + ly bot.
-__device__ __forceinline__ void se_src(int o, float scale, int in, int& i0, int& i1, float& l1) {
-#pragma clang fp contract(off)
-    const float r = fmaxf(__builtin_fmaf(scale, (float)o + 0.5f, -0.5f), 0.f);
-    i0 = (int)r;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + ((i0 < in - 1) ? 1 : 0);
-    l1 = r - (float)i0;
-}
-__device__ __forceinline__ float se_tap(float a, float b, float c, float d, float ly, float lx) {
-#pragma clang fp contract(off)
-    const float hy = 1.f - ly, hx = 1.f - lx;
-    const float top = __builtin_fmaf(hx, a, lx * b);
-    const float bot = __builtin_fmaf(hx, c, lx * d);
-    const float t = hy * top, u = ly * bot;
-    return t + u;
-}
 
 struct SegEnsArgs {
     const float* a;
@@ -59,12 +36,6 @@ struct SegEnsArgs {
     int stage_cap;       // floats of stage (0: every tap through L1)
     int tiles_x, ntiles;
 };
-
-// exp(x) for x <= 0 as one v_exp_f32: the relative error grows with |x| ((|x| + 1) * 6e-8), the value shrinks as exp(x): no
-// probability is off by more than 1e-7 (tests: prob against float64, beside the composed fp32 path)
-__device__ __forceinline__ float se_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
-
-constexpr int SE_SMALL = 24;             // identity: channels a thread keeps in registers -- one read of the logits (VOC: 21)
 
 // Identity, C <= SE_SMALL (the VOC form).  r1 / r2: channel 0 of the wave's row segment (the same for all lanes: the loads take a
 // scalar base and the lane as offset, so SE_SMALL of them per student are in flight without an address register each).  Both
@@ -188,51 +159,6 @@ __device__ __forceinline__ void se_pixel_any(const float* q1, const float* q2, l
         if (e > me) { me = e; be = c; }
         if (prob) prob[(long)c * HW] = e;
     }
-}
-
-// Stage the source pixels under the output tile at (ty0, tx0), both students, where they fit stage_cap floats (every thread of the
-// workgroup calls this: two barriers).  The source index is monotone in the output coordinate, so the first row's y0 and the last
-// row's y1 bound every tap of the tile (the same for the columns).  Returns whether the tile is staged; fy0, fx0, fw: the footprint.
-__device__ __forceinline__ bool se_stage_tile(const float* __restrict__ pa, const float* __restrict__ pb, float* st, int tid, int ty0,
-                                              int tx0, int C, int h, int w, int H, int W, float sy, float sx, int stage_cap, int& fy0,
-                                              int& fx0, int& fw) {
-    const int Cp = (C + 3) & ~3;
-    const long hw = (long)h * w;
-    int i1, j0;
-    float l;
-    const int ty1 = ty0 + SE_TH - 1 < H ? ty0 + SE_TH - 1 : H - 1, tx1 = tx0 + SE_TW - 1 < W ? tx0 + SE_TW - 1 : W - 1;
-    se_src(ty0, sy, h, fy0, i1, l);
-    se_src(ty1, sy, h, j0, i1, l);
-    const int fh = i1 - fy0 + 1;
-    se_src(tx0, sx, w, fx0, i1, l);
-    se_src(tx1, sx, w, j0, i1, l);
-    fw = i1 - fx0 + 1;
-    const bool staged = (long)fh * fw * 2 * Cp <= (long)stage_cap;
-    __syncthreads();                           // the previous tile's taps are read
-    if (staged) {
-        // read in source order (consecutive threads on consecutive columns), written channel-fastest
-        const int plane = fh * fw, n = 2 * Cp * plane;
-        for (int i = tid; i < n; i += SE_THREADS) {
-            const int pc = i / plane, rq = i - pc * plane, r = rq / fw, q = rq - r * fw;
-            const int sidx = pc >= Cp ? 1 : 0, c = pc - sidx * Cp;
-            const float* src = (sidx ? pb : pa) + (long)c * hw;
-            st[(rq * 2 + sidx) * Cp + c] = c < C ? src[(long)(fy0 + r) * w + fx0 + q] : 0.f;
-        }
-    }
-    __syncthreads();
-    return staged;
-}
-
-// the floats of stage a launch asks for: an upper bound of a tile's footprint (the kernels check every tile's own footprint against
-// it), 0 where that does not fit SE_STAGE or nothing is interpolated
-inline int se_stage_floats(int C, int h, int w, int H, int W) {
-    if (h == H && w == W) return 0;
-    const double sy = (double)h / H, sx = (double)w / W;
-    long fh = (long)((SE_TH - 1) * sy) + 4, fw = (long)((SE_TW - 1) * sx) + 4;
-    if (fh > h) fh = h;
-    if (fw > w) fw = w;
-    const long need = fh * fw * 2 * ((C + 3) & ~3);
-    return need <= SE_STAGE ? (int)need : 0;
 }
 
 __global__ __launch_bounds__(SE_THREADS) void seg_ens_kernel(const SegEnsArgs a) {

@@ -6,6 +6,7 @@ current torch stream.  Outputs are freshly allocated unless an `out=` is given.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import Optional, Sequence
 
@@ -1511,3 +1512,68 @@ def seg_boundary(gt: Tensor, pred: Tensor, *, num_classes: int, max_dist: int, b
     desc.workspace, desc.workspace_bytes = ws.data_ptr(), nbytes
     L().dupl_seg_boundary(ctypes.byref(desc), _stream())
     return band_hist, (biou if d > 0 else None), dg, dp
+
+
+# ------------------------------------------------------------------------------------------ confidence calibration (csrc/seg_calib.hip)
+def inv_temperature(T: float) -> float:
+    """The fp32 1 / T as a Python float: THE inverse temperature of a temperature, for tools/eval_seg (which scores it) and
+    tools/predict (which applies it with scale_) alike, so that both multiply the logits by the same bits."""
+    T = float(T)
+    if not (math.isfinite(T) and T > 0.0):
+        raise ValueError(f"a temperature must be finite and positive, got {T}")
+    with np.errstate(over="ignore", divide="ignore"):
+        inv = float(np.float32(1.0) / np.float32(T))
+    if not (math.isfinite(inv) and inv > 0.0):
+        raise ValueError(f"the temperature {T} has no positive finite fp32 inverse")
+    return inv
+
+
+def seg_calibration(a: Tensor, b: Optional[Tensor] = None, size=None, *, gt: Tensor, temperatures=(1.0,), nbins: int = 15,
+                    is_prob: bool = False, bins: Optional[Tensor] = None, cls: Optional[Tensor] = None, sums: Optional[Tensor] = None):
+    """One image's calibration counters, one pass over the (H,W) = size grid (csrc/seg_calib.hip).  a (and b, the second student):
+    (C,h,w) or (1,C,h,w) logits; per temperature T_t the SOURCE logits are multiplied by inv_temperature(T_t) (one fp32 rounding,
+    what scale_ leaves), then winner and conf are seg_decide's on those logits, bit for bit.  is_prob: a (and b) are probabilities
+    at the output size (DenseCRF's marginals); temperatures must then be (1.0,).  gt (H,W) int64; values outside [0, C) are skipped.
+      bins (T, nbins, 3) int64 += per bin min(int(conf * nbins), nbins - 1): pixels, pixels with winner == gt, sum of rint(conf * 2^24);
+      cls  (T, C, 3)     int64 += the same per predicted class;
+      sums (T, 4)        int64 += valid pixels, correct pixels, sum of rint(nll * 2^20), sum of rint(brier * 2^24).
+    The outputs that are given are added to and the others left out; with none given all three are allocated (zeroed).
+    Returns (bins, cls, sums), None for what was left out.  No synchronisation with the device."""
+    if a.dim() == 4:
+        assert a.shape[0] == 1 and (b is None or b.shape[0] == 1), "seg_calibration takes one image per call"
+        a, b = a[0], (b[0] if b is not None else None)
+    assert a.dim() == 3 and (b is None or a.shape == b.shape), f"a, b: (C,h,w) of equal shape, got {tuple(a.shape)}"
+    C, h, w = a.shape
+    H, W = (h, w) if size is None else (int(size[0]), int(size[1]))
+    if not 1 <= C <= _lib.SEG_CALIB_MAX_C:
+        raise ValueError(f"seg_calibration takes 1 .. {_lib.SEG_CALIB_MAX_C} channels, got {C}")
+    temps = [float(t) for t in temperatures]
+    if not 1 <= len(temps) <= _lib.SEG_CALIB_MAX_T:
+        raise ValueError(f"seg_calibration takes 1 .. {_lib.SEG_CALIB_MAX_T} temperatures, got {len(temps)}")
+    nbins = int(nbins)
+    if not 1 <= nbins <= _lib.SEG_CALIB_MAX_BINS:
+        raise ValueError(f"nbins must be 1 .. {_lib.SEG_CALIB_MAX_BINS}, got {nbins}")
+    inv = [inv_temperature(t) for t in temps]
+    if is_prob and (h, w) != (H, W):
+        raise ValueError(f"seg_calibration(is_prob=True) takes probabilities at the output size {(H, W)}, got {(h, w)}")
+    if is_prob and temps != [1.0]:
+        raise ValueError(f"seg_calibration(is_prob=True) has no temperature to apply: temperatures must be (1.0,), got {tuple(temps)}")
+    T = len(temps)
+    a = _chk(a.contiguous())
+    b = _chk(b.contiguous()) if b is not None else None
+    dev = a.device
+    assert gt.is_cuda and gt.dtype == torch.int64 and gt.numel() == H * W, f"gt: (H,W) int64 on the device, got {tuple(gt.shape)}"
+    gt = gt.contiguous()
+    if bins is None and cls is None and sums is None:
+        bins = torch.zeros((T, nbins, 3), device=dev, dtype=torch.int64)
+        cls = torch.zeros((T, C, 3), device=dev, dtype=torch.int64)
+        sums = torch.zeros((T, 4), device=dev, dtype=torch.int64)
+    for name, t, shape in (("bins", bins, (T, nbins, 3)), ("cls", cls, (T, C, 3)), ("sums", sums, (T, 4))):
+        assert t is None or (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and tuple(t.shape) == shape), \
+            f"{name} must be {shape} int64, got {tuple(t.shape)}"
+    host_inv = (ctypes.c_float * T)(*inv)
+    d = _lib.SegCalibDesc(C=C, h=h, w=w, H=H, W=W, is_prob=int(bool(is_prob)), T=T, nbins=nbins, a=a.data_ptr(), b=_p(b),
+                          gt=gt.data_ptr(), inv_temp=ctypes.cast(host_inv, ctypes.c_void_p).value, bins=_p(bins), cls=_p(cls),
+                          sums=_p(sums))
+    L().dupl_seg_calib(ctypes.byref(d), _stream())
+    return bins, cls, sums

@@ -18,7 +18,12 @@ boundaries: per image and column one fused pass (ops.seg_boundary, csrc/boundary
 distance to the nearest ground-truth label change and fills the Boundary IoU counters (Cheng et al., CVPR 2021); the trimap mIoU of
 every `--trimap_widths` width (DeepLab's trimap score) and the Boundary IoU are printed under the table, returned under the key
 "boundary" of every score dict and, with `--crf 1`, reported for seg_crf too, so the CRF's effect at the boundary reads off one run.
-`--crf_method {exact,lattice}` chooses the CRF stage's inference (utils/dcrf.py).  Without these flags nothing changes."""
+`--crf_method {exact,lattice}` chooses the CRF stage's inference (utils/dcrf.py).  `--calibration 1` scores whether the confidence
+tools/predict publishes means anything: per image and column one fused pass (ops.seg_calibration, csrc/seg_calib.hip) bins the
+winner's confidence against the ground truth at every temperature of `--temp_sweep` at once -- ECE, MCE, NLL, Brier, reliability
+bins, risk-coverage and the temperature of least NLL, printed under the boundary lines, returned under the key "calibration" and
+written in full to `--calib_json`; with `--crf 1` the CRF's marginals are scored at T = 1.  The confidence scored at T is, bit for
+bit, what `predict --temperature T` writes.  Without these flags nothing changes."""
 from collections import OrderedDict
 
 import torch
@@ -136,25 +141,80 @@ def format_boundary(scores, name_list):
                      for s, n in zip(scores, name_list))
 
 
+def parse_temp_sweep(text):
+    """--temp_sweep "LO:HI:N" -> the temperatures of one pass: 1.0 first, then the geometric grid LO .. HI of N points (rounded to 12
+    significant digits, so 0.5:4:13 holds 2.0 itself) without its own 1.0.  0 < LO < HI, 2 <= N <= 15: with T = 1 at most
+    evaluate.CALIB_MAX_T = 16 temperatures."""
+    import argparse
+    try:
+        lo, hi, n = str(text).strip().split(":")
+        lo, hi, n = float(lo), float(hi), int(n)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a temperature sweep is LO:HI:N, got {text!r}")
+    if not (0.0 < lo < hi < float("inf")) or not 2 <= n <= evaluate.CALIB_MAX_T - 1:
+        raise argparse.ArgumentTypeError(f"a temperature sweep needs 0 < LO < HI and 2 <= N <= {evaluate.CALIB_MAX_T - 1}, got {text!r}")
+    grid = [float(f"{lo * (hi / lo) ** (i / (n - 1)):.12g}") for i in range(n)]
+    return (1.0,) + tuple(t for t in grid if t != 1.0)
+
+
+def calibration_scores(cm):
+    """The "calibration" entry of a score dict, from a filled evaluate.CalibrationMatrix: {"temperatures", "nbins", "scores": one
+    dict per temperature (CalibrationMatrix.scores; index 0 is T = 1), "best": CalibrationMatrix.best_temperature}."""
+    sc = cm.scores()
+    return {"temperatures": list(cm.temperatures), "nbins": cm.nbins, "scores": sc, "best": cm.best_temperature(sc)}
+
+
+def format_calibration(scores, name_list):
+    """One line per column: the scores at T = 1, then the temperature of least NLL with ECE and NLL there."""
+    lines = []
+    for s, n in zip(scores, name_list):
+        c = s["calibration"]
+        one, best = c["scores"][0], c["best"]
+        line = (f"calibration {n}: ECE {one['ece']:.4f} MCE {one['mce']:.4f} NLL {one['nll']:.4f} Brier {one['brier']:.4f} "
+                f"conf {one['mean_conf']:.4f} acc {one['acc']:.4f} at T=1")
+        if len(c["scores"]) > 1 and best["index"] is not None:
+            at = c["scores"][best["index"]]
+            line += f" | best T {best['T_grid']:.4g} (fit {best['T_fit']:.4g}): ECE {at['ece']:.4f} NLL {at['nll']:.4f}"
+            if best["at_edge"]:
+                line += " -- at the end of the sweep: widen --temp_sweep"
+        lines.append(line)
+    return "\n".join(lines)
+
+
+def _calibration_matrices(calibration, n, num_classes, dev):
+    return [evaluate.CalibrationMatrix(num_classes, dev, **calibration) for _ in range(n)] if calibration else None
+
+
+def _calibration_update(cals, seg, labels):
+    """One image into every column's CalibrationMatrix: each student alone, then (a third matrix) the two together."""
+    for k in range(2):
+        cals[k].update(labels, seg[k])
+    if len(cals) > 2:
+        cals[2].update(labels, seg[0], seg[1])
+
+
 def _boundary_matrices(boundary, n, num_classes, dev):
     return [evaluate.BoundaryMatrix(num_classes, dev, max_dist=max(boundary)) for _ in range(n)] if boundary else None
 
 
 def validate_coco(model, data_loader, args, num_classes=81, cat_list=None, process_group=None, keep_logits=None, ensemble=False,
-                  boundary=None):
+                  boundary=None, calibration=None):
     """eval_seg_coco_ddp._validate on this rank's shard of the loader (the reference splits the val set round-robin over
     the ranks, tools/eval_seg_coco_ddp.py:239-245, and every rank scores its own shard).  With `process_group` (or an
     initialised default group) the per-rank confusion matrices are additionally summed over the ranks -- nc^2 int64
     counters, the only exchange of the evaluation path -- so that every rank returns the scores of the WHOLE set.
     ensemble=True: one fused pass per image (ops.seg_ensemble) up-samples both students' logits, scores each student and the mean
     of their class probabilities -> (seg_score_1, seg_score_2, seg_score_ens); the students' scores are the same counts.
-    boundary=widths: every column also feeds an evaluate.BoundaryMatrix and its score dict gains "boundary" (boundary_scores)."""
+    boundary=widths: every column also feeds an evaluate.BoundaryMatrix and its score dict gains "boundary" (boundary_scores).
+    calibration={"temperatures", "nbins"}: every column also feeds an evaluate.CalibrationMatrix -- the up-sampling form, from the
+    low-resolution logits -- and its score dict gains "calibration" (calibration_scores)."""
     import torch.distributed as dist
     from ..utils.train_helper import _device_of, _fetch
     dev = _device_of(model)
     cms = [evaluate.ConfusionMatrix(num_classes, dev) for _ in range(2)]
     em = evaluate.EnsembleMatrix(num_classes, dev) if ensemble else None
     bms = _boundary_matrices(boundary, 3 if ensemble else 2, num_classes, dev)
+    cals = _calibration_matrices(calibration, 3 if ensemble else 2, num_classes, dev)
     model.eval()
     scales = getattr(args, "scales", (1.0, 1.25, 1.5))
     for data in data_loader:
@@ -163,6 +223,8 @@ def validate_coco(model, data_loader, args, num_classes=81, cat_list=None, proce
         H, W = labels.shape[1:]
         if ensemble:
             _ensemble_update(em, bms, seg, labels)
+        if cals:
+            _calibration_update(cals, seg, labels)
         for k in range(2):
             if not ensemble or bms:
                 pred = ops.upsample_argmax(seg[k], H, W)
@@ -173,36 +235,47 @@ def validate_coco(model, data_loader, args, num_classes=81, cat_list=None, proce
             if keep_logits is not None:          # eval_seg_coco_ddp.py:127-128 saves the summed low-resolution logits
                 keep_logits(data[0], k + 1, seg[k])
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
-        for t in ([em.hist, em.counts] if ensemble else [c.hist for c in cms]) + [t for b in bms or [] for t in (b.hist, b.biou)]:
+        for t in (([em.hist, em.counts] if ensemble else [c.hist for c in cms]) + [t for b in bms or [] for t in (b.hist, b.biou)] +
+                  [t for c in cals or [] for t in c.tensors()]):
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
     sc = _ensemble_scores(em) if ensemble else [c.scores() for c in cms]
     for s, b in zip(sc, bms or []):
         s["boundary"] = boundary_scores(b, boundary)
+    for s, c in zip(sc, cals or []):
+        s["calibration"] = calibration_scores(c)
     if cat_list is not None:
         print(format_tabs(sc, ["Seg_1", "Seg_2", "Seg_ens"][:len(sc)], cat_list=cat_list))
         if bms:
             print(format_boundary(sc, ["Seg_1", "Seg_2", "Seg_ens"]))
+        if cals:
+            print(format_calibration(sc, ["Seg_1", "Seg_2", "Seg_ens"]))
     return tuple(sc)
 
 
-def validate(model, data_loader, args, num_classes=21, cat_list=None, keep_logits=None, ensemble=False, boundary=None):
+def validate(model, data_loader, args, num_classes=21, cat_list=None, keep_logits=None, ensemble=False, boundary=None,
+             calibration=None):
     """eval_seg_voc._validate: multi-scale seg predictions of both students over a loader of
     (name, inputs (1,3,h,w), labels (1,H,W), cls_label) -> (seg_score_1, seg_score_2).
     keep_logits(name, branch, logits) is called with the (1,C1,H,W) device logits (the reference np.save()s them for the
     CRF stage).  ensemble=True: one fused pass per image (ops.seg_ensemble) scores each student and the mean of their class
     probabilities -> (seg_score_1, seg_score_2, seg_score_ens); the students' scores are the same counts.
-    boundary=widths: every column also feeds an evaluate.BoundaryMatrix and its score dict gains "boundary" (boundary_scores)."""
+    boundary=widths: every column also feeds an evaluate.BoundaryMatrix and its score dict gains "boundary" (boundary_scores).
+    calibration={"temperatures", "nbins"}: every column also feeds an evaluate.CalibrationMatrix -- the identity form, the logits are
+    at label size -- and its score dict gains "calibration" (calibration_scores)."""
     from ..utils.train_helper import _device_of, _fetch
     dev = _device_of(model)
     cms = [evaluate.ConfusionMatrix(num_classes, dev) for _ in range(2)]
     em = evaluate.EnsembleMatrix(num_classes, dev) if ensemble else None
     bms = _boundary_matrices(boundary, 3 if ensemble else 2, num_classes, dev)
+    cals = _calibration_matrices(calibration, 3 if ensemble else 2, num_classes, dev)
     model.eval()
     for data in data_loader:
         inputs, labels, _ = _fetch(data, dev)
         seg = msc_seg_logits(model, inputs, labels.shape[1:], getattr(args, "scales", (1.0, 1.5, 1.25)))
         if ensemble:
             _ensemble_update(em, bms, seg, labels)
+        if cals:
+            _calibration_update(cals, seg, labels)
         for k in range(2):
             if not ensemble or bms:
                 pred = ops.argmax_channels(seg[k])
@@ -215,27 +288,34 @@ def validate(model, data_loader, args, num_classes=21, cat_list=None, keep_logit
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         # main() shards the split over the ranks for both datasets: the score is of the summed confusion matrices
-        for t in ([em.hist, em.counts] if ensemble else [c.hist for c in cms]) + [t for b in bms or [] for t in (b.hist, b.biou)]:
+        for t in (([em.hist, em.counts] if ensemble else [c.hist for c in cms]) + [t for b in bms or [] for t in (b.hist, b.biou)] +
+                  [t for c in cals or [] for t in c.tensors()]):
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
     sc = _ensemble_scores(em) if ensemble else [c.scores() for c in cms]
     for s, b in zip(sc, bms or []):
         s["boundary"] = boundary_scores(b, boundary)
+    for s, c in zip(sc, cals or []):
+        s["calibration"] = calibration_scores(c)
     if cat_list is not None and (not dist.is_initialized() or dist.get_rank() == 0):
         print(format_tabs(sc, ["Seg_1", "Seg_2", "Seg_ens"][:len(sc)], cat_list=cat_list))
         if bms:
             print(format_boundary(sc, ["Seg_1", "Seg_2", "Seg_ens"]))
+        if cals:
+            print(format_calibration(sc, ["Seg_1", "Seg_2", "Seg_ens"]))
     return tuple(sc)
 
 
 def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb_dir, num_classes, dev, process_group=None,
-             boundary=None, method=None):
+             boundary=None, method=None, calibration=None):
     """tools/eval_seg_voc.py:94-153 / tools/eval_seg_coco_ddp.py:142-202 on the device, over this rank's `names`: per image the
     saved logits of `branch` are resized to the JPEG's size, softmax + DenseCRF(10, 1, 1, 4, 121, 5) + argmax run on the device,
     the label PNG (and the palette PNG) are written and a device ConfusionMatrix is accumulated; with several ranks the
     matrices are summed.  image_path(name) -> JPEG path; label_of(name, image) -> (H,W) ground truth.  Returns the scores.
     branch "ens": both students' saved logits go through ops.seg_ensemble and the CRF runs on the mean of their probabilities.
     method "exact" / "lattice": the CRF's inference (None = utils.dcrf.METHOD).  boundary=widths: the predictions also feed an
-    evaluate.BoundaryMatrix and the returned dict gains "boundary" (boundary_scores)."""
+    evaluate.BoundaryMatrix and the returned dict gains "boundary" (boundary_scores).  calibration={"nbins", ...}: the CRF's marginals
+    also feed an evaluate.CalibrationMatrix as probabilities, at T = 1 only (they are not a soft-max of the logits, no temperature
+    is fitted for them), and the returned dict gains "calibration" (calibration_scores)."""
     import os
     import numpy as np
     import torch.distributed as dist
@@ -247,6 +327,7 @@ def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb
         post.method = method
     cm = evaluate.ConfusionMatrix(num_classes, dev)
     bm = evaluate.BoundaryMatrix(num_classes, dev, max_dist=max(boundary)) if boundary else None
+    cal = evaluate.CalibrationMatrix(num_classes, dev, temperatures=(1.0,), nbins=calibration["nbins"]) if calibration else None
     for d in (segs_dir, segs_rgb_dir):
         if d:
             os.makedirs(d, exist_ok=True)
@@ -269,16 +350,20 @@ def crf_proc(branch, names, image_path, label_of, logits_dir, segs_dir, segs_rgb
         cm.update(label, pred)
         if bm is not None:
             bm.update(label, pred)
+        if cal is not None:
+            cal.update(label, Q, is_prob=True)
         pred = pred.cpu().numpy().astype(np.uint8)
         Image.fromarray(pred).save(os.path.join(segs_dir, name + ".png"))
         if segs_rgb_dir:
             Image.fromarray(imutils.encode_cmap(pred).astype(np.uint8)).save(os.path.join(segs_rgb_dir, name + ".png"))
     if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
-        for t in [cm.hist] + ([bm.hist, bm.biou] if bm is not None else []):
+        for t in [cm.hist] + ([bm.hist, bm.biou] if bm is not None else []) + (cal.tensors() if cal is not None else []):
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=process_group)
     sc = cm.scores()
     if bm is not None:
         sc["boundary"] = boundary_scores(bm, boundary)
+    if cal is not None:
+        sc["calibration"] = calibration_scores(cal)
     return sc
 
 
@@ -329,6 +414,17 @@ def build_parser(dataset: str = "voc"):
                         "last line, a 'boundary' entry in every returned score dict; with --crf 1 for seg_crf too")
     p.add_argument("--trimap_widths", default="1,2,4,8,16,32", type=parse_trimap_widths,
                    help="the trimap widths --boundary 1 reports: positive integers, ascending, at most 64")
+    p.add_argument("--calibration", default=0, type=int, choices=(0, 1),
+                   help="1: also score every column's confidence calibration (one fused pass per image and column, ops.seg_calibration): "
+                        "a line per column with ECE, MCE, NLL, Brier, mean confidence and accuracy at T = 1 and the temperature of least "
+                        "NLL, '<column> ECE' in the last line, a 'calibration' entry in every returned score dict; with --crf 1 the CRF's "
+                        "marginals at T = 1 too.  The temperature goes into predict --temperature")
+    p.add_argument("--calib_bins", default=15, type=int, help="the confidence bins of --calibration 1: 1 .. 64")
+    p.add_argument("--temp_sweep", default="0.5:4:13", type=parse_temp_sweep,
+                   help="the temperatures --calibration 1 sweeps in its one pass, LO:HI:N: a geometric grid of N <= 15 points beside T = 1")
+    p.add_argument("--calib_json", default=None, type=str,
+                   help="--calibration 1: write every column's full calibration dict (reliability bins, risk-coverage, classes, per "
+                        "temperature) to this JSON file")
     p.add_argument("--nograd_gemm", default=os.environ.get("DUPL_NOGRAD_GEMM", "f16x3"), choices=("f16x3", "f16"),
                    help="GEMMs and attention of the no-grad encoder passes (multi-scale CAM, validation, inference): f16x3 = three f16 products, "
                         "fp32-equivalent (default); f16 = one product on the hi planes, fp32 accumulation (engine.set_nograd_gemm_mode; "
@@ -343,6 +439,13 @@ def check_branch_args(args):
     """Refuse flag combinations that cannot be served, before anything is loaded."""
     if args.crf_branch == "ens" and not args.ensemble:
         raise SystemExit(ENS_NEEDS_FLAG)
+    if not 1 <= getattr(args, "calib_bins", 15) <= evaluate.CALIB_MAX_BINS:
+        raise SystemExit(f"--calib_bins must be 1 .. {evaluate.CALIB_MAX_BINS}, got {args.calib_bins}")
+
+
+def calibration_spec(args):
+    """The calibration= argument of validate / validate_coco / crf_proc from the flags; None without --calibration 1."""
+    return {"temperatures": tuple(args.temp_sweep), "nbins": int(args.calib_bins)} if args.calibration else None
 
 
 def pick_crf_branch(choice, s1, s2, ens=None):
@@ -421,13 +524,15 @@ def main(argv=None):
             np.save(os.path.join(logits_dir, f"branch{branch}", str(nm) + ".npy"), {"msc_seg": logits.cpu().numpy()})
 
     boundary = args.trimap_widths if args.boundary else None
+    calibration = calibration_spec(args)
+    extra = {"calibration": calibration} if calibration else {}
     with torch.no_grad():
         if is_voc:
             sc = validate(model, loader, args, args.num_classes, voc.class_list, keep_logits=keep, ensemble=bool(args.ensemble),
-                          boundary=boundary)
+                          boundary=boundary, **extra)
         else:
             sc = validate_coco(model, loader, args, args.num_classes, coco.class_list, keep_logits=keep, ensemble=bool(args.ensemble),
-                               boundary=boundary)
+                               boundary=boundary, **extra)
     s1, s2 = sc[0], sc[1]
     ens = sc[2] if args.ensemble else None
     last = {"Seg_1 mIoU": s1["miou"], "Seg_2 mIoU": s2["miou"]}
@@ -435,10 +540,22 @@ def main(argv=None):
         last.update({"Seg_ens mIoU": ens["miou"], "agree": ens["agree"]})
     if boundary:
         last.update({f"{n} BIoU": s["boundary"]["biou"] for n, s in zip(("Seg_1", "Seg_2", "Seg_ens"), sc)})
+    calib_out = {}
+    if calibration:
+        last.update({f"{n} ECE": s["calibration"]["scores"][0]["ece"] for n, s in zip(("Seg_1", "Seg_2", "Seg_ens"), sc)})
+        calib_out = {n: s["calibration"] for n, s in zip(("Seg_1", "Seg_2", "Seg_ens"), sc)}
     # crf_proc (eval_seg_voc.py:185-188): the student with the higher mIoU unless --crf_branch / --ensemble say otherwise
     branch = pick_crf_branch(args.crf_branch, s1, s2, ens)
     rank0 = int(os.environ.get("RANK", "0")) == 0
+
+    def write_calib_json():
+        if calibration and args.calib_json and rank0:
+            import json
+            with open(args.calib_json, "w") as f:
+                json.dump(calib_out, f, indent=1)
+
     if not args.crf:
+        write_calib_json()
         if rank0:
             over = "both students' logits under " + logits_dir if branch == "ens" else f"{logits_dir}/{branch}"
             print({**last, "next": f"DenseCRF over {over} (reference: crf_proc, CPU)"})
@@ -465,13 +582,19 @@ def main(argv=None):
         print("crf post-processing...")
     with torch.no_grad():
         crf = crf_proc(branch, names, image_path, label_of, logits_dir, os.path.join(base_dir, "segs/seg_preds", args.infer_set),
-                       rgb_dir, args.num_classes, dev, boundary=boundary, method=args.crf_method)
+                       rgb_dir, args.num_classes, dev, boundary=boundary, method=args.crf_method, **extra)
     if rank0:
         print(format_tabs([crf], ["seg_crf"], cat_list=voc.class_list if is_voc else coco.class_list))
         if boundary:
             print(format_boundary([crf], ["seg_crf"]))
             last["seg_crf BIoU"] = crf["boundary"]["biou"]
+        if calibration:
+            print(format_calibration([crf], ["seg_crf"]))
+            last["seg_crf ECE"] = crf["calibration"]["scores"][0]["ece"]
         print({**last, "seg_crf mIoU": crf["miou"]})
+    if calibration:
+        calib_out["seg_crf"] = crf["calibration"]
+        write_calib_json()
     return tuple(sc) + (crf,)
 
 

@@ -10,7 +10,8 @@ ops.msc_seg_accum_ consumes), optionally DenseCRF, then ONE pass that turns the 
 the rejection of low-confidence pixels and the per-class statistics (ops.seg_decide), optionally the connected regions of that map (ops.seg_regions: --regions 1 lists the objects with class, area, box
 and mean confidence; --min_region N first absorbs the regions of fewer than N pixels into their surroundings,
 ops.seg_regions_clean), and one integer pass for the palette overlay (ops.seg_paint).  Nothing but the PNGs' pixels, 2 (C+1)
-counters and, when asked for, the region table travel to the host."""
+counters and, when asked for, the region table travel to the host.  `--temperature T` (the temperature eval_seg --calibration 1
+reports) multiplies the logits by the fp32 1 / T before that pass: the confidence written is then the one eval_seg scored at T."""
 import argparse
 import json
 import os
@@ -135,7 +136,7 @@ def device_palette(dev):
 
 def predict_image(model, image_u8, *, scales=(1.0, 1.5, 1.25), branch="ens", window=0, stride=0, window_batch=8, crf=False,
                   min_conf=0.0, ignore_index=255, alpha=0.6, contour=False, tint_background=False, contour_rgb=(255, 255, 255),
-                  crf_method="exact", min_region=0, regions=False, connectivity=8, max_regions=4096):
+                  crf_method="exact", min_region=0, regions=False, connectivity=8, max_regions=4096, temperature=1.0):
     """image_u8 (H,W,3) uint8 (numpy or tensor) -> dict(label (H,W) uint8, conf (H,W) fp32, overlay (H,W,3) uint8 -- device tensors --,
     stats (2, C+1) int64 on the host: ops.seg_decide's, windows: the windows per scale).  branch 1 / 2: that student, "ens": the
     mean of the two students' class probabilities.  crf: DenseCRF with crf_proc's parameters on the chosen student's logits or on
@@ -144,7 +145,10 @@ def predict_image(model, image_u8, *, scales=(1.0, 1.5, 1.25), branch="ens", win
     min_region > 0: the connected regions (connectivity 4 / 8) of fewer than min_region pixels are absorbed by their surroundings
     (ops.seg_regions_clean) before painting; label, overlay and stats then describe the cleaned map (the rejected pixels stay), and
     `cleaned` = {regions, pixels} says what moved.  regions: also region (H,W) int32 (device), n_regions and region_table, the first
-    max_regions rows of ops.seg_regions's table on the host.  With neither, the dict has the keys above and no region op runs."""
+    max_regions rows of ops.seg_regions's table on the host.  With neither, the dict has the keys above and no region op runs.
+    temperature T != 1: the accumulated logits of the chosen branch (of both, for "ens") are multiplied by ops.inv_temperature(T)
+    before the decision -- the confidence is then, bit for bit, the one eval_seg --calibration 1 scored at T (the label of a single
+    student does not change); at exactly 1.0 no op is added.  Refused together with crf (TEMPERATURE_WITH_CRF)."""
     from ..datasets.device_loader import DeviceTransform
     from ..utils.train_helper import _device_of
     branch = str(branch)
@@ -158,6 +162,10 @@ def predict_image(model, image_u8, *, scales=(1.0, 1.5, 1.25), branch="ens", win
         raise ValueError(f"connectivity must be 4 or 8, got {connectivity}")
     if int(max_regions) < 1:
         raise ValueError(f"max_regions must be at least 1, got {max_regions}")
+    temperature = float(temperature)
+    inv_t = ops.inv_temperature(temperature)
+    if crf and temperature != 1.0:
+        raise ValueError(TEMPERATURE_WITH_CRF)
     if window and not stride:
         stride = default_stride(window)
     check_window_args(window, stride)
@@ -169,6 +177,9 @@ def predict_image(model, image_u8, *, scales=(1.0, 1.5, 1.25), branch="ens", win
     inputs = DeviceTransform(dev).val_item(raw)[None]
     seg = msc_seg_logits_windowed(model, inputs, (H, W), scales, window, stride, window_batch)
     C = seg[0].shape[1]
+    if temperature != 1.0:                     # nothing else reads the accumulated logits: scaled in place
+        for k in ((0, 1) if branch == "ens" else (int(branch) - 1,)):
+            ops.scale_(seg[k], inv_t)
     stats = torch.zeros((2, C + 1), device=dev, dtype=torch.int64)
     kw = dict(min_conf=min_conf, ignore_index=ignore_index, stats=stats)
     if crf:
@@ -202,6 +213,10 @@ def predict_image(model, image_u8, *, scales=(1.0, 1.5, 1.25), branch="ens", win
                             contour=contour, contour_rgb=contour_rgb)
     return {"label": label, "conf": conf, "overlay": overlay, "stats": stats.cpu(),
             "windows": windows_per_scale(H, W, scales, window, stride), **extra}
+
+
+TEMPERATURE_WITH_CRF = ("--temperature cannot be combined with --crf 1: the CRF's marginals are not a soft-max of these logits, and "
+                        "eval_seg --calibration 1 fits no temperature for them")
 
 
 def class_summary(stats, names, n_pixels):
@@ -272,6 +287,10 @@ def build_parser():
                    help="how --crf 1 evaluates the DenseCRF messages: exact = the dense sum over all pixel pairs (default), lattice = "
                         "the permutohedral-lattice approximation (O(N) per message); summary.json records it when given")
     p.add_argument("--min_conf", default=0.0, type=float, help="pixels whose confidence is below this get the label 255")
+    p.add_argument("--temperature", default=None, type=float,
+                   help="divide the logits by T before the soft-max (eval_seg --calibration 1 reports the T of least NLL): changes the "
+                        "confidence -- what --min_conf, mean_conf and conf/<stem>.png see --, not a single student's labels; default 1 = off; "
+                        "not with --crf 1; summary.json records it when given")
     p.add_argument("--alpha", default=0.6, type=float, help="weight of the class colour in the overlay, 0 .. 1")
     p.add_argument("--contour", default=0, type=int, choices=(0, 1), help="1: draw the class boundaries in white")
     p.add_argument("--tint_background", default=0, type=int, choices=(0, 1), help="1: blend the background's colour in as well")
@@ -296,6 +315,8 @@ def parse_args(argv=None):
     args = build_parser().parse_args(argv)
     args.crf_method_given = args.crf_method is not None          # summary.json records the method only when the flag is given
     args.crf_method = args.crf_method or "exact"
+    args.temperature_given = args.temperature is not None        # summary.json records the temperature only when the flag is given
+    args.temperature = 1.0 if args.temperature is None else args.temperature
     args.scales = tuple(float(v) for v in str(args.scales).strip("()[] ").split(",") if v.strip())
     if not args.scales:
         raise SystemExit("--scales: at least one scale")
@@ -317,6 +338,12 @@ def parse_args(argv=None):
         raise SystemExit(f"--region_min_pixels must be at least 1, got {args.region_min_pixels}")
     if args.max_regions < 1:
         raise SystemExit(f"--max_regions must be at least 1, got {args.max_regions}")
+    try:
+        ops.inv_temperature(args.temperature)
+    except ValueError as e:
+        raise SystemExit(f"--temperature: {e}")
+    if args.temperature != 1.0 and args.crf:
+        raise SystemExit(TEMPERATURE_WITH_CRF)
     return args
 
 
@@ -349,7 +376,8 @@ def main(argv=None):
                           window_batch=args.window_batch, crf=bool(args.crf), min_conf=args.min_conf, alpha=args.alpha,
                           contour=bool(args.contour), tint_background=bool(args.tint_background), crf_method=args.crf_method,
                           **({"min_region": args.min_region, "regions": bool(args.regions), "connectivity": args.connectivity,
-                              "max_regions": args.max_regions} if args.min_region or args.regions else {}))
+                              "max_regions": args.max_regions} if args.min_region or args.regions else {}),
+                          **({"temperature": args.temperature} if args.temperature != 1.0 else {}))
         png = Image.fromarray(r["label"].cpu().numpy())        # mode L; attaching the palette makes it an index image (mode P)
         png.putpalette(flat_palette)
         png.save(os.path.join(args.out_dir, "labels", stem + ".png"))
@@ -375,7 +403,7 @@ def main(argv=None):
     with open(os.path.join(args.out_dir, "summary.json"), "w") as f:
         json.dump({"scales": list(args.scales), "branch": args.branch, "window": args.window, "stride": args.stride if args.window else 0,
                    "crf": int(args.crf), **({"crf_method": args.crf_method} if args.crf_method_given else {}),
-                   "min_conf": args.min_conf,
+                   "min_conf": args.min_conf, **({"temperature": args.temperature} if args.temperature_given else {}),
                    **({"min_region": args.min_region, "cleaned": {k: sum(e["cleaned"][k] for e in summary) for k in ("regions", "pixels")}}
                       if args.min_region else {}),
                    "images": summary}, f, indent=1)

@@ -172,3 +172,88 @@ class BoundaryMatrix:
             iu = I / (G + P - I)
         present = G > 0
         return {"biou": float(np.nanmean(iu[present])) if present.any() else float("nan"), "iou": dict(zip(range(len(iu)), iu))}
+
+
+CALIB_MAX_T, CALIB_MAX_BINS = 16, 64      # DUPL_SEG_CALIB_MAX_T, DUPL_SEG_CALIB_MAX_BINS
+
+
+class CalibrationMatrix:
+    """Device-resident calibration counters of one score column, filled image by image by the fused pass ops.seg_calibration
+    (csrc/seg_calib.hip) at every temperature of `temperatures` at once: bins (T, nbins, 3), cls (T, nc, 3) and sums (T, 4) int64
+    (pixels, correct pixels and fixed-point sums, as the op documents them).  All are plain sums: all-reduce them.  The confidence
+    they bin is, bit for bit, what tools/predict --temperature T writes."""
+
+    def __init__(self, num_classes, device, temperatures=(1.0,), nbins=15):
+        self.num_classes, self.nbins = int(num_classes), int(nbins)
+        self.temperatures = tuple(float(t) for t in temperatures)
+        if not 1 <= len(self.temperatures) <= CALIB_MAX_T:
+            raise ValueError(f"1 .. {CALIB_MAX_T} temperatures go through one pass, got {len(self.temperatures)}")
+        if not 1 <= self.nbins <= CALIB_MAX_BINS:
+            raise ValueError(f"nbins must be 1 .. {CALIB_MAX_BINS}, got {nbins}")
+        for t in self.temperatures:
+            ops.inv_temperature(t)
+        T = len(self.temperatures)
+        self.bins = torch.zeros((T, self.nbins, 3), device=device, dtype=torch.int64)
+        self.cls = torch.zeros((T, self.num_classes, 3), device=device, dtype=torch.int64)
+        self.sums = torch.zeros((T, 4), device=device, dtype=torch.int64)
+
+    def tensors(self):
+        return [self.bins, self.cls, self.sums]
+
+    def update(self, gt, a, b=None, size=None, is_prob=False):
+        """gt (H,W) or (1,H,W) int64; a (and b): the logits (1,C,h,w) or (C,h,w) of one or two students, up-sampled to `size`
+        (None: gt's size); is_prob: probabilities at gt's size, scored at T = 1 only (temperatures must be (1.0,))."""
+        H, W = gt.shape[-2:]
+        ops.seg_calibration(a, b, (H, W) if size is None else size, gt=gt.reshape(H, W), temperatures=self.temperatures,
+                            nbins=self.nbins, is_prob=is_prob, bins=self.bins, cls=self.cls, sums=self.sums)
+
+    def scores(self):
+        """One dict per temperature: T, n, ece = sum_b n_b / n |acc_b - conf_b|, mce (the largest gap of a non-empty bin), nll, brier,
+        acc, mean_conf, reliability [{n, acc, conf} per bin], risk_coverage [{min_conf, coverage, acc} for k = 0 .. nbins - 1: the
+        pixels in bins >= k, what --min_conf k / nbins keeps up to the fp32 rounding of conf * nbins], classes {predicted class:
+        {n, precision, mean_conf}}.  Empty bins and classes give nan."""
+        bins, cls, sums = (t.cpu().numpy().astype(np.float64) for t in self.tensors())
+        out = []
+        with np.errstate(divide="ignore", invalid="ignore"):
+            for t, T in enumerate(self.temperatures):
+                n = sums[t, 0]
+                nb, okb, cfb = bins[t, :, 0], bins[t, :, 1], bins[t, :, 2] / float(1 << 24)
+                acc_b, conf_b = okb / nb, cfb / nb
+                gap = np.abs(acc_b - conf_b)
+                full = nb > 0
+                keep_n, keep_ok = np.cumsum(nb[::-1])[::-1], np.cumsum(okb[::-1])[::-1]
+                nc, okc, cfc = cls[t, :, 0], cls[t, :, 1], cls[t, :, 2] / float(1 << 24)
+                out.append({
+                    "T": T, "n": int(n),
+                    "ece": float(np.sum(nb[full] / n * gap[full])) if n else float("nan"),
+                    "mce": float(gap[full].max()) if full.any() else float("nan"),
+                    "nll": float(sums[t, 2] / float(1 << 20) / n), "brier": float(sums[t, 3] / float(1 << 24) / n),
+                    "acc": float(sums[t, 1] / n), "mean_conf": float(cfb.sum() / n) if n else float("nan"),
+                    "reliability": [{"n": int(nb[k]), "acc": float(acc_b[k]), "conf": float(conf_b[k])} for k in range(self.nbins)],
+                    "risk_coverage": [{"min_conf": k / self.nbins, "coverage": float(keep_n[k] / n), "acc": float(keep_ok[k] / keep_n[k])}
+                                      for k in range(self.nbins)],
+                    "classes": {c: {"n": int(nc[c]), "precision": float(okc[c] / nc[c]), "mean_conf": float(cfc[c] / nc[c])}
+                                for c in range(self.num_classes)},
+                })
+        return out
+
+    def best_temperature(self, scores=None):
+        """{"T_grid": the temperature of the grid with the least mean NLL (the lowest such on equal NLL), "T_fit": the vertex of the
+        parabola through it and its two neighbours in log T -- T_grid itself where the minimum sits at an end of the grid, "at_edge":
+        whether it does (the sweep should then be widened), "index": T_grid's index in `temperatures`}."""
+        sc = self.scores() if scores is None else scores
+        order = sorted(range(len(sc)), key=lambda i: sc[i]["T"])
+        nll = [sc[i]["nll"] for i in order]
+        if any(np.isnan(v) for v in nll):
+            return {"T_grid": float("nan"), "T_fit": float("nan"), "at_edge": True, "index": None}
+        j = min(range(len(order)), key=lambda k: (nll[k], k))
+        Tg = sc[order[j]]["T"]
+        edge = j == 0 or j == len(order) - 1
+        fit = Tg
+        if not edge:
+            x0, x1, x2 = (float(np.log(sc[order[k]]["T"])) for k in (j - 1, j, j + 1))
+            y0, y1, y2 = nll[j - 1], nll[j], nll[j + 1]
+            den = (x1 - x0) * (y1 - y2) - (x1 - x2) * (y1 - y0)
+            if den != 0.0:
+                fit = float(np.exp(x1 - 0.5 * ((x1 - x0) ** 2 * (y1 - y2) - (x1 - x2) ** 2 * (y1 - y0)) / den))
+        return {"T_grid": Tg, "T_fit": fit, "at_edge": edge, "index": order[j]}

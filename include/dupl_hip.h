@@ -956,6 +956,49 @@ typedef struct dupl_seg_boundary_desc {
 int64_t dupl_seg_boundary_workspace(const dupl_seg_boundary_desc* d);
 int dupl_seg_boundary(const dupl_seg_boundary_desc* d, dupl_stream_t stream);
 
+/* ------------------------------------------------------------------ confidence calibration of one image (csrc/seg_calib.hip)
+ * Beyond the reference.  Whether the confidence dupl_seg_decide publishes means anything: one pass over the (H,W) grid bins it
+ * against a ground truth, at T temperatures at once.  Per pixel with 0 <= gt < C and per temperature index t:
+ *   v_s[src] = a_s[src] * inv_temp[t]: ONE fp32 multiply of every SOURCE logit, before any up-sampling and never contracted into
+ *            what follows -- the bits dupl_scale(a_s, inv_temp[t]) leaves in the buffer;
+ *   winner, conf = what dupl_seg_decide returns on v (the same taps, the same order of sums; one student, two, or with is_prob the
+ *            probabilities themselves): bit for bit; with inv_temp[t] = 1.0f what it returns on the raw logits;
+ *   bin    = min((int)(conf * (float)nbins), nbins - 1), the product in fp32;
+ *   one student, u = the up-sampled v, m = max_c u, x_c = exp(u_c - m) (the kernel's one-instruction exp), s = sum_c x_c in float64:
+ *            nll   = logf((float)s) - (u_gt - m)                 (the logit domain: finite whatever the logits)
+ *            brier = (float)(sum_c x_c^2 in float64) * conf^2 - 2 (x_gt * conf) + 1,   conf = 1 / (float)s
+ *   two students or is_prob, p = the mean of the two soft-maxes (dupl_seg_ensemble's prob) or the given probabilities (their mean):
+ *            nll   = -logf(max(p_gt, FLT_MIN))
+ *            brier = (float)(sum_c p_c^2 in float64) - 2 p_gt + 1
+ *   nll enters the sum as min(nll, DUPL_SEG_CALIB_NLL_MAX).
+ * Outputs, int64, ADDED to, each optional, at least one required:
+ *   bins (T, nbins, 3): per confidence bin the pixels, the pixels with winner == gt, the sum of (int64)rintf(conf * 2^24)
+ *            (dupl_seg_decide's fixed point);
+ *   cls  (T, C, 3):     the same three numbers per predicted class (winner);
+ *   sums (T, 4):        valid pixels, correct pixels, sum of (int64)rintf(nll * 2^20), sum of (int64)rintf(brier * 2^24).
+ * Integer atomics only, combined per workgroup first: bit-reproducible.  One launch, no host synchronisation. */
+#define DUPL_SEG_CALIB_MAX_C 255
+#define DUPL_SEG_CALIB_MAX_T 16
+#define DUPL_SEG_CALIB_MAX_BINS 64
+#define DUPL_SEG_CALIB_NLL_MAX 1048576.0f
+typedef struct dupl_seg_calib_desc {
+    uint32_t struct_size;        /* sizeof(dupl_seg_calib_desc), checked */
+    int32_t C, h, w;             /* a, b: (C,h,w) fp32; 1 <= C <= DUPL_SEG_CALIB_MAX_C */
+    int32_t H, W;                /* output grid */
+    int32_t is_prob;             /* != 0: the inputs are probabilities; requires (h,w) == (H,W), T == 1 and inv_temp[0] == 1.0f */
+    int32_t T;                   /* temperatures: 1 .. DUPL_SEG_CALIB_MAX_T */
+    int32_t nbins;               /* confidence bins: 1 .. DUPL_SEG_CALIB_MAX_BINS */
+    int32_t reserved0;           /* 0 */
+    const float* a;              /* student 1 */
+    const float* b;              /* student 2; or NULL */
+    const int64_t* gt;           /* (H,W) ground truth; values outside [0, C) are skipped */
+    const float* inv_temp;       /* HOST array of T floats, each finite and > 0 (validated here) */
+    int64_t* bins;               /* (T, nbins, 3); or NULL */
+    int64_t* cls;                /* (T, C, 3); or NULL */
+    int64_t* sums;               /* (T, 4); or NULL */
+} dupl_seg_calib_desc;
+int dupl_seg_calib(const dupl_seg_calib_desc* d, dupl_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,5 @@
 """Micro-timings of the small (non-GEMM) kernels of the step at their step shapes, through dupl_amd.ops (torch events on the
-current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd | seg_render | predict | crf_lattice | regions | boundary
+current stream, 200 launches each).  Usage: python tools/op_bench.py [ln_bwd] [ln_fwd] [split] [attn_bwd] [crf] [cam_eval] [seg_ensemble] | backbone | nograd | seg_render | predict | crf_lattice | regions | boundary | calibration
 `crf` (only when named: it runs for seconds) times DenseCRF(10, 1, 1, 4, 121, 5) and its launches at 375x500x21 and 480x640x81.
 `cam_eval` (only when named) times the fused tail of tools/infer_cam (ops.cam_eval) against the composed path it replaces.
 `seg_ensemble` (only when named) times the fused ensemble tail of tools/eval_seg --ensemble 1 (ops.seg_ensemble) against the composition
@@ -15,6 +15,10 @@ a 1024 x 2048 single-label map, after asserting that ids, areas and boxes agree.
 and 480x640x81 against ops.confusion_accum on the same maps (what eval_seg --boundary 1 adds per image and column), against the host
 path (.cpu() -> the scipy filters and erosions of tests/boundary_ref.py, equality asserted first) and against the 16 B/px of reading the
 two int64 maps once; its three kernels are timed apart through a second call that stops after each of them.
+`calibration` (only when named; then nothing else runs) times ops.seg_calibration (all three counter tables, 15 bins) at the VOC form
+(375x500x21, identity) and the COCO form (480x640x81 from 28x28), one and two students, at T = 1 and at 14 temperatures, against the
+composition that yields the same counters -- scale_ -> seg_decide -> read-back -> numpy bincount, once per temperature, equality asserted
+first -- and against its two floors: the bytes read once, and the v_exp_f32 instructions of the soft-max.
 `predict` (only when named; then nothing else runs) times tools/predict on one synthetic 1024 x 2048 image, ViT-B, whole image against
 sliding windows, with the peak device memory of each.
 `backbone` (only when named; then nothing else runs) times one phase-B training step at VOC 448^2, 4 images, two student streams
@@ -399,6 +403,73 @@ def boundary_bench(dev, g):
                   f"column); host scipy path {t_h:.0f} us ({t_h / t_b:.0f}x)")
 
 
+def calibration_bench(dev, g):
+    """ops.seg_calibration into resident counters (what evaluate.CalibrationMatrix.update enqueues per image and column) on seeded
+    N(0, 2^2) logits and a seeded ground truth with 5 % ignored pixels.  Floors: the logits and the int64 gt read once at 6.3 TB/s;
+    the v_exp_f32 the definition needs -- per pixel, temperature and student C for one student (the partition sum), 2 C for two
+    (partition sum, then the mean; where the values stay in registers the second sweep reuses the first's) -- at 8 cycles per
+    wave instruction on 1024 SIMDs at 2.4 GHz."""
+    import os
+    import time
+    import numpy as np
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import calib_ref as CR
+    import ctypes
+    from dupl_amd import _lib
+    nbins = 15
+    sweep = (1.0,) + tuple(float(f"{0.45 * (4.2 / 0.45) ** (i / 12):.12g}") for i in range(13))
+    for name, C, (h, w), (H, W) in (("VOC", 21, (375, 500), (375, 500)), ("COCO", 81, (28, 28), (480, 640))):
+        z = [(torch.randn((C, h, w), generator=g) * 2).to(dev) for _ in range(2)]
+        gt_h = torch.randint(0, C, (H, W), generator=g)
+        gt_h[torch.rand((H, W), generator=g) < 0.05] = 255
+        gt, gt_np = gt_h.to(dev), gt_h.numpy()
+        for students in (1, 2):
+            ins = z[:students]
+            for temps in ((1.0,), sweep):
+                T = len(temps)
+                bins = torch.zeros((T, nbins, 3), device=dev, dtype=torch.int64)
+                cls = torch.zeros((T, C, 3), device=dev, dtype=torch.int64)
+                sums = torch.zeros((T, 4), device=dev, dtype=torch.int64)
+                call = lambda: ops.seg_calibration(*ins, size=(H, W), gt=gt, temperatures=temps, nbins=nbins, bins=bins, cls=cls, sums=sums)
+
+                def composed():
+                    out = []
+                    for t in temps:
+                        label, conf = ops.seg_decide(*[ops.scale_(v.clone(), ops.inv_temperature(t)) for v in ins], size=(H, W))
+                        out.append(CR.host_counters(label.cpu().numpy(), conf.cpu().numpy(), gt_np, C, nbins))
+                    return out
+                # the launch alone: a descriptor built once (the wrapper's checks, inverse temperatures and ctypes struct are host time)
+                inv = (ctypes.c_float * T)(*[ops.inv_temperature(t) for t in temps])
+                desc = _lib.SegCalibDesc(C=C, h=h, w=w, H=H, W=W, T=T, nbins=nbins, a=ins[0].data_ptr(), b=ins[1].data_ptr() if students == 2
+                                         else None, gt=gt.data_ptr(), inv_temp=ctypes.cast(inv, ctypes.c_void_p).value, bins=bins.data_ptr(),
+                                         cls=cls.data_ptr(), sums=sums.data_ptr())
+                fn, ref, stream = ops.L().dupl_seg_calib, ctypes.byref(desc), ops._stream()
+                only = _lib.SegCalibDesc.from_buffer_copy(desc)                  # sums alone: the same pixels, 4 T counters to flush
+                only.bins = only.cls = None
+                ref_only = ctypes.byref(only)
+                call()
+                want = composed()
+                for t in range(T):
+                    assert np.array_equal(bins[t].cpu().numpy(), want[t][0]) and np.array_equal(cls[t].cpu().numpy(), want[t][1])
+                    assert sums[t, :2].tolist() == want[t][2].tolist()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(3):
+                    composed()
+                t_c = (time.perf_counter() - t0) * 1e6 / 3
+                nbytes = 4 * C * h * w * students + 8 * H * W
+                n_exp = T * H * W * C * (1 if students == 1 else 2) * students
+                f_mem, f_exp = nbytes / 6.3e6, n_exp / 64 * 8 / (1024 * 2.4e3)
+                for i in range(3):
+                    t_w = timeit(call, n=100, warm=10)
+                    t_k = timeit(lambda: fn(ref, stream), n=100, warm=10)
+                    t_s = timeit(lambda: fn(ref_only, stream), n=100, warm=10)
+                    print(f"calibration {name} {H}x{W}x{C} from {h}x{w}, {students} student(s), T={T}, round {i}: seg_calibration {t_w:.1f} us "
+                          f"through ops, {t_k:.1f} us the launch alone, {t_s:.1f} us with sums alone ({t_k * 1e3 / (H * W * T):.3f} ns per pixel and temperature; floors: {nbytes / 1e6:.2f} MB = {f_mem:.1f} us at 6.3 TB/s, "
+                          f"{n_exp / 1e6:.1f} M v_exp_f32 = {f_exp:.1f} us: {max(f_mem, f_exp) / t_k:.2f} of the larger); composed "
+                          f"scale_ -> seg_decide -> read-back -> bincount x {T}: {t_c:.0f} us ({t_c / t_k:.0f}x)")
+
+
 def _count_only(label):
     """dupl_seg_regions asked for n_regions alone: the labelling launches without number and stats"""
     import ctypes
@@ -530,6 +601,8 @@ def main():
         return regions_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     if "boundary" in sys.argv[1:]:
         return boundary_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
+    if "calibration" in sys.argv[1:]:
+        return calibration_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     if "crf_lattice" in sys.argv[1:]:
         return crf_lattice_bench(torch.device("cuda:0"), torch.Generator().manual_seed(0))
     which = set(sys.argv[1:]) or {"ln_bwd", "ln_fwd", "split", "attn_bwd", "multi", "cam"}

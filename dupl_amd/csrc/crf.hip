@@ -25,6 +25,7 @@
 #include "common.h"
 #include "../../include/dupl_hip.h"
 #include "crf_softmax.h"
+#include <float.h>
 #include <math.h>
 
 namespace {
@@ -229,7 +230,9 @@ __global__ __launch_bounds__(256) void crf_unary_kernel(const float* __restrict_
         for (int c = 0; c < C; ++c) {
             const long o = (long)c * N + i;
             const float p = mode == 1 ? expf(in[o] - mx) / s : in[o];
-            U[o] = -logf(fminf(fmaxf(p, 1e-5f), 1.f));
+            // the logarithm in fp64, rounded once: logf is v_log_f32 (log2, 1 ulp) times ln 2, and an ulp of log2(1e-5) = -16.6 is
+            // 1.4 ulp of the result 11.5 -- measured 2 fp32 values off the correctly rounded energy at the clip
+            U[o] = (float)-log((double)fminf(fmaxf(p, 1e-5f), 1.f));
         }
     }
 }
@@ -251,11 +254,17 @@ inline int crf_gauss_radius(float sxy) {
     return r > 1.0e6 ? 1000000 : (int)ceil(r);
 }
 
+// log2(e) / (2 s^2), the factor of the squared distance in the exponent, saturated at FLT_MAX: for s below ~4.6e-20 the fp32
+// quotient is +inf, and inf * 0 (the distance of j = i) would make k(i,i), n and every output NaN.  At FLT_MAX a distance of 0
+// still gives k = 1 and every other one (>= 1: pixel and colour coordinates are integers) under-flows k to 0 -- the limit
+// k = delta_ij of s -> 0.  Every finite quotient is left as it is.
+inline float crf_exp_scale(float s) { return fminf(CRF_HALF_LOG2E / (s * s), FLT_MAX); }
+
 // one application of one kernel.  Q == nullptr: out (N) = n.  img == nullptr: Gaussian kernel (srgb unused).
 void crf_message_launch(const uint8_t* img, const float* Q, const float* nrm, float* out, int C, int H, int W, float sxy, float srgb,
                         hipStream_t s) {
     const long N = (long)H * W;
-    const float ax = CRF_HALF_LOG2E / (sxy * sxy), ac = img ? CRF_HALF_LOG2E / (srgb * srgb) : 0.f;
+    const float ax = crf_exp_scale(sxy), ac = img ? crf_exp_scale(srgb) : 0.f;
     if (!img) {
         const long R = crf_gauss_radius(sxy), win = 2 * R + 1;
         if (win * win < N) {

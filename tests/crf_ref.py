@@ -126,3 +126,75 @@ def rel_err(a, ref):
 def top2_margin(Q):
     t = Q.topk(2, dim=0).values
     return t[0] - t[1]
+
+
+# ---------------------------------------------------------------------------- helpers of tests/test_crf_edges_gpu.py
+# (H, W) whose pixel counts sit on, one short of and one past the sizes of the device tiling: 32 (an MFMA tile), 64 (a wave's
+# queries), 128 (a key tile, a row-sum half block), 256 (a query block), 512
+SEAM_SHAPES = ((31, 1), (4, 8), (3, 11), (7, 9), (5, 13), (1, 127), (128, 1), (3, 43), (15, 17), (16, 16), (1, 257), (7, 73), (19, 27))
+SEAM_N = (31, 32, 33, 63, 65, 127, 128, 129, 255, 256, 257, 511, 513)
+CHUNK_C = (1, 31, 32, 33, 64, 65)                           # around the 32-channel chunk of the dense kernel
+# dense_crf with a zero weight: (H, W, C) x (w_g, w_b), the other parameters those of PARAMS["eval"].  The seed is chosen so
+# that NO pixel of the fp64 result has a top-2 margin under MARGIN (600 pixels: REF_TIE_SHARE admits none).
+BRANCH_CASES = ((20, 30, 21), (20, 30, 33))
+BRANCH_WEIGHTS = ((0.0, 4.0), (1.0, 0.0), (0.0, 0.0))
+BRANCH_T = 10
+EXTREME_STD = (1e-25, 1e-19, 1e-3, 1e6, 3e38)
+
+
+def branch_seed(H, W, C):
+    return case_seed(H, W) + C + 500
+
+
+def gauss_radius(sxy):
+    """The radius of the truncated Gaussian window as csrc/crf.hip documents it (crf_gauss_radius): the mass outside a disc of
+    radius R, 2 pi s^2 exp(-R^2 / 2 s^2), is below 2^-32, i.e. R = ceil(s sqrt(2 (ln(2 pi s^2 + 1) + 32 ln 2))), capped at 10^6."""
+    s = float(sxy)
+    r = s * math.sqrt(2.0 * (math.log(2.0 * math.pi * s * s + 1.0) + 32.0 * math.log(2.0)))
+    return 1000000 if r > 1.0e6 else int(math.ceil(r))
+
+
+def gauss_takes_stencil(H, W, sxy):
+    """Whether the Gaussian kernel runs as the truncated stencil: only when its square window is smaller than the image."""
+    win = 2 * gauss_radius(sxy) + 1
+    return win * win < H * W
+
+
+def wide_range_q(C, H, W, seed, scale=25.0):
+    """Q (C, H*W) fp32 = softmax over the channels of `scale` x unit Gaussian logits, evaluated in fp64 and rounded: the entries
+    span from 1 down to the fp32 denormals (and to 0 below them); channel 1 is exactly 0 everywhere."""
+    g = torch.Generator().manual_seed(seed)
+    z = scale * torch.randn((C, H * W), generator=g, dtype=torch.float64)
+    z[1] = -math.inf
+    return torch.softmax(z, 0).float()
+
+
+def decades(Q):
+    """log10 of the ratio of the largest to the smallest positive entry."""
+    pos = Q[Q > 0].double()
+    return float(torch.log10(pos.max() / pos.min()))
+
+
+def ulp_distance(a, b):
+    """Number of fp32 values between a and b, elementwise (+0 and -0 are the same value); a, b finite fp32."""
+    def order(t):
+        i = t.contiguous().view(torch.int32).to(torch.int64)
+        return torch.where(i < 0, -(i & 0x7FFFFFFF), i)
+    return (order(a.float()) - order(b.float())).abs()
+
+
+def unary_exact(p):
+    """-log(clip(p, 1e-5f, 1)) of fp32 p: the clip in fp32 as the device does it (exact), the logarithm in fp64, rounded once."""
+    return (-torch.log(p.float().clamp(1e-5, 1.0).double())).float()
+
+
+def unary_from_logits(z, dtype=torch.float64):
+    """-log(clip(softmax_c(z), 1e-5, 1)) with everything in `dtype`; z (C, N)."""
+    return -torch.log(torch.softmax(z.to(dtype), 0).clamp(1e-5, 1.0))
+
+
+def unary_from_any_labels(labels, n, gt_prob):
+    """unary_from_labels for labels that may lie outside [0, n): such a pixel gets the "other" energy in every channel."""
+    e_gt, e_other = -math.log(gt_prob), -math.log((1.0 - gt_prob) / (n - 1))
+    hit = labels.reshape(1, -1) == torch.arange(n).reshape(-1, 1)
+    return torch.where(hit, torch.tensor(e_gt, dtype=torch.float32), torch.tensor(e_other, dtype=torch.float32))

@@ -159,3 +159,84 @@ def test_seeded_inputs_are_non_trivial_and_nearly_tie_free(H, W, C, pset):
     assert float(close.float().mean()) <= R.REF_TIE_SHARE
     assert bool(((Q32.argmax(0) == Q64.argmax(0)) | close).all())
     assert err32 < 1e-4
+
+
+# ---------------------------------------------------------------------------- what tests/test_crf_edges_gpu.py relies on
+def test_gauss_radius_restatement_against_hand_values():
+    """sigma = 1: ln(2 pi + 1) = 1.98555, + 32 ln 2 = 22.18071 -> 24.16626, x 2 = 48.33252, sqrt = 6.95216 -> R = 7, a 15 x 15
+    window (225 pixels).  sigma = 3: ln(18 pi + 1) = 4.05264 -> 26.23335, x 2 = 52.46670, sqrt = 7.24339, x 3 = 21.7302 -> R = 22,
+    a 45 x 45 window (2025 pixels).  The mass outside the disc is below 2^-32 at R and not at R - 1."""
+    assert R.gauss_radius(1.0) == 7 and R.gauss_radius(3.0) == 22
+    assert abs(math.sqrt(2 * (1.98555 + 22.18071)) - 6.95216) < 1e-4 and abs(3 * math.sqrt(2 * (4.05264 + 22.18071)) - 21.7302) < 1e-3
+    for s in (1.0, 3.0, 0.5, 10.0):
+        r = R.gauss_radius(s)
+        assert 2 * math.pi * s * s * math.exp(-r * r / (2 * s * s)) < 2.0 ** -32
+        assert 2 * math.pi * s * s * math.exp(-(r - 2) ** 2 / (2 * s * s)) > 2.0 ** -32      # ceil and the "+ 1" cost under 2 pixels
+    assert R.gauss_radius(1e6) == 1000000 and R.gauss_radius(3e38) == 1000000 and R.gauss_radius(1e-25) == 1
+    # the shapes of the GPU test on either side of win^2 = N
+    assert not R.gauss_takes_stencil(15, 15, 1.0)                                             # 225 < 225 is false: dense
+    assert R.gauss_takes_stencil(2, 113, 1.0) and R.gauss_takes_stencil(226, 1, 1.0) and R.gauss_takes_stencil(33, 33, 1.0)
+    assert not R.gauss_takes_stencil(40, 25, 3.0)
+    assert 33 > 2 * 7 + 1                                                                     # 33 x 33 has unclipped windows
+    assert all(not R.gauss_takes_stencil(H, W, 3.0) for H, W in R.SEAM_SHAPES)
+    assert all(R.gauss_takes_stencil(9, 13, s) for s in R.EXTREME_STD[:3]) and not any(R.gauss_takes_stencil(9, 13, s) for s in R.EXTREME_STD[3:])
+
+
+def test_seam_shapes_have_the_pixel_counts_they_are_named_for():
+    assert tuple(H * W for H, W in R.SEAM_SHAPES) == R.SEAM_N
+    assert {(3, 43), (15, 17), (16, 16), (19, 27)} <= set(R.SEAM_SHAPES)
+    assert any(H == 1 for H, W in R.SEAM_SHAPES) and any(W == 1 for H, W in R.SEAM_SHAPES)
+
+
+def test_wide_range_q_spans_thirty_decades():
+    Q = R.wide_range_q(21, 24, 40, seed=5)
+    tiny = float(np.finfo(np.float32).tiny)
+    assert Q.dtype == torch.float32 and Q.shape == (21, 960) and bool((Q >= 0).all())
+    print(f"wide_range_q: {R.decades(Q):.1f} decades, {int(((Q > 0) & (Q < tiny)).sum())} denormals, {int((Q == 0).sum())} zeros")
+    assert R.decades(Q) >= 30.0
+    assert int(((Q > 0) & (Q < tiny)).sum()) >= 10                          # denormals included
+    assert bool((Q[1] == 0).all()) and bool((Q[0] > 0).any())
+    assert float((Q.double().sum(0) - 1).abs().max()) < 1e-6
+    # within single pixels too, not only across the image: the median pixel's own entries span 30 decades
+    pos = torch.where(Q > 0, Q.double(), torch.ones((), dtype=torch.float64))
+    assert float(torch.log10(Q.double().amax(0) / pos.amin(0)).median()) >= 30.0
+
+
+def test_ulp_distance_and_exact_unary():
+    one, nxt = np.float32(1.0), np.nextafter(np.float32(1.0), np.float32(2.0))
+    a = torch.tensor([0.0, -0.0, one, one, -one, 1e-45, 3.0])
+    b = torch.tensor([-0.0, 0.0, nxt, np.nextafter(nxt, np.float32(2.0)), -nxt, -1e-45, 3.0])
+    assert R.ulp_distance(a, b).tolist() == [0, 0, 1, 2, 1, 2, 0]
+    lo = np.float32(1e-5)
+    p = torch.tensor([0.0, 1e-45, 1e-6, np.nextafter(lo, np.float32(0)), lo, np.nextafter(lo, np.float32(1)), 0.5, 1.0, 1.5])
+    U = R.unary_exact(p)
+    at_lo = np.float32(-math.log(float(lo)))
+    assert U.dtype == torch.float32 and U[:5].tolist() == [float(at_lo)] * 5 and float(U[5]) <= float(at_lo)
+    assert float(R.unary_exact(torch.tensor([1.1e-5]))) == float(np.float32(-math.log(float(np.float32(1.1e-5))))) < float(at_lo)
+    assert float(U[6]) == float(np.float32(math.log(2.0))) and U[7:].tolist() == [0.0, 0.0]
+    lab = torch.tensor([[-1, 0, 1, 2, 255]])
+    Ul = R.unary_from_any_labels(lab, 2, 0.999)
+    g, o = float(np.float32(-math.log(0.999))), float(np.float32(-math.log(0.001)))
+    assert Ul.tolist() == [[o, g, o, o, o], [o, o, g, o, o]]
+    assert torch.equal(R.unary_from_any_labels(torch.tensor([[0, 1, 1]]), 2, 0.5), R.unary_from_labels(torch.tensor([[0, 1, 1]]), 2, 0.5).reshape(2, -1))
+
+
+@pytest.mark.parametrize("H,W,C", R.BRANCH_CASES)
+def test_zero_weight_cases_are_tie_free(H, W, C):
+    """The dense_crf cases with a zero weight (tests/test_crf_edges_gpu.py), on the fp64 reference alone: the share of pixels
+    with a top-2 margin under MARGIN stays under REF_TIE_SHARE, a plain fp32 evaluation has the fp64 labels, and each kernel on
+    its own still changes labels."""
+    img, _, logits = R.make_case(H, W, C, seed=R.branch_seed(H, W, C))
+    prob = torch.softmax(logits, 0)
+    U = R.unary_from_softmax(prob)
+    p = R.PARAMS["eval"]
+    for w_g, w_b in R.BRANCH_WEIGHTS:
+        Q64 = R.mean_field(img, U, R.BRANCH_T, w_g, p["sxy_g"], w_b, p["sxy_b"], p["srgb_b"])
+        Q32 = R.mean_field(img, U, R.BRANCH_T, w_g, p["sxy_g"], w_b, p["sxy_b"], p["srgb_b"], dtype=torch.float32)
+        close = R.top2_margin(Q64) < R.MARGIN
+        changed = float((Q64.argmax(0) != prob.argmax(0)).float().mean())
+        print(f"({H},{W},{C}) w_g={w_g} w_b={w_b}: {int(close.sum())} pixels with margin < {R.MARGIN} (smallest "
+              f"{float(R.top2_margin(Q64).min()):.2e}), argmax changed at {100 * changed:.1f} %")
+        assert float(close.float().mean()) <= R.REF_TIE_SHARE
+        assert bool(((Q32.argmax(0) == Q64.argmax(0)) | close).all())
+        assert (changed > 0.02) == (w_g != 0.0 or w_b != 0.0)
